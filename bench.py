@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X BA hot path (one Gauss-Newton step of optimizeExtrinsics).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config config4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config config4] [--dump-outputs DIR] [--full]
+
+A plain run sets up the headline workload, ramps the clocks, runs W warmup steps, times exactly K
+steps and prints one JSON line (metric, value, unit, ms_per_step, ...); with --dump-outputs DIR it
+also writes what the K-th timed step left (DIR/params.npy, see dump_outputs).  Everything else this
+file measures -- the event-timed kernel windows and the roofline, the per-step distribution, the
+other configs, shards and strong-scaling lines, the real optimizeExtrinsics calls, the parity check
+against the oracle and the CPU baselines -- runs only with --full (where --no-cpu, --no-parity and
+--no-extra still drop their parts).
 
 One "step" = one pass of the hot path over the whole problem: linearisation of every corner
 (residual + Jacobian), normal-equation reduction, Schur solve, float32 update
@@ -17,11 +25,11 @@ writes its system into every peer's inbox over xGMI and solves) when the handsha
 every rank, else with one RCCL all-reduce (MCC_TRANSPORT=rccl forces it).
 
 Timing: an untimed clock ramp (>= --ramp-seconds of steps, the same step count on every rank),
-W warmup steps, then exactly K steps between barriers (max over ranks); the dominant kernel(s)
-are then timed with HIP events over a window of 100 further steps, and the per-step distribution
-(median, p10, p90) over 30 event-timed windows of 20 graph-launched steps.
+W warmup steps, then exactly K steps between barriers (max over ranks); with --full the dominant
+kernel(s) are then timed with HIP events over a window of 100 further steps, and the per-step
+distribution (median, p10, p90) over 30 event-timed windows of 20 graph-launched steps.
 
-Extra keys (same JSON line):
+Extra keys (same JSON line, --full only):
   * N = 1: "configs" -- the other BASELINE configs (2, 3, 5) at full size on this GPU (ms per
     step, corner evals/s, linearisation time and HBM-roofline fraction, traffic and FP64 from the
     committed rocprofv3 summaries);
@@ -133,10 +141,9 @@ def load_profile(prefix: str, config: str, n_views: int):
     return best
 
 
-def measure(ba, steps: int, warmup: int, ramp_s: float, window: int):
+def timed_steps(ba, steps: int, warmup: int, ramp_s: float):
     """Clock ramp (same step count on every rank: each step may exchange with the peers),
-    W warmup steps, K timed steps between barriers (max over ranks), then the HIP-event window
-    of the dominant kernel over `window` launches."""
+    W warmup steps, K timed steps between barriers (max over ranks): the headline figure."""
     ba.step(8)
     ba.synchronize()
     t0 = time.perf_counter()
@@ -157,6 +164,12 @@ def measure(ba, steps: int, warmup: int, ramp_s: float, window: int):
     ba.barrier()
     t1 = time.perf_counter()
     dt = ba.allreduce_max(t1 - t0)
+    return dict(dt=dt, ramp={"steps": n_ramp + 24, "seconds": round(ramp_wall, 3)})
+
+
+def kernel_timing(ba, window: int):
+    """After timed_steps: the HIP-event window of the dominant kernel over `window` launches, the
+    exchange time and the per-step distribution (runs of their own, untimed for the headline)."""
     ba.timing_begin()
     ba.step(window)
     lin_ms, step_ms_ev, nlaunch = ba.timing_end()
@@ -183,8 +196,26 @@ def measure(ba, steps: int, warmup: int, ramp_s: float, window: int):
         ba.check()
     dist.update(unit="ms per step", windows=DIST_WINDOWS, steps_per_window=DIST_STEPS,
                 launch="graph" if graph else "eager", timer="HIP events between back-to-back windows (max over ranks)")
-    return dict(dt=dt, lin_ms=lin_ms, step_ms_ev=step_ms_ev, nlaunch=nlaunch, xchg_ms=xchg_ms, n_xchg=n_xchg,
-                ramp={"steps": n_ramp + 24, "seconds": round(ramp_wall, 3)}, dist=dist)
+    return dict(lin_ms=lin_ms, step_ms_ev=step_ms_ev, nlaunch=nlaunch, xchg_ms=xchg_ms, n_xchg=n_xchg, dist=dist)
+
+
+def measure(ba, steps: int, warmup: int, ramp_s: float, window: int):
+    """timed_steps, then kernel_timing: the full measurement of one problem."""
+    m = timed_steps(ba, steps, warmup, ramp_s)
+    m.update(kernel_timing(ba, window))
+    return m
+
+
+def dump_outputs(ba, directory: str, rank: int, world: int):
+    """What a caller of the timed path holds after its last timed step: the parameter vector
+    (mcc_get_params: camera poses, then photo poses, 6 floats each; float32, a few hundred KB at
+    most for the BASELINE configs) as DIR/params.npy (params_rank<r>.npy for N > 1: each rank owns
+    its photo shard).  The rig is seeded and the default ramp runs the step factor 0.95^(k+1) down to a
+    zero float32 update long before the timed region, so the vector does not depend on how many
+    steps the time-sized ramp took."""
+    os.makedirs(directory, exist_ok=True)
+    name = "params.npy" if world == 1 else f"params_rank{rank}.npy"
+    np.save(os.path.join(directory, name), ba.get_params().astype(np.float32))
 
 
 def lin_kernels(ba) -> str:
@@ -449,10 +480,16 @@ def main():
     ap.add_argument("--config", default="config4")
     ap.add_argument("--views", type=int, default=None, help="views per rank (default: the config's)")
     ap.add_argument("--ramp-seconds", type=float, default=0.25, help="untimed clock ramp before the warmup")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the parameter vector they left as DIR/params.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also: kernel windows and roofline, step distribution, the other configs, shards, strong "
+                         "scaling, the optimize key, the oracle parity check and the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the per-config / strong-scaling extra keys")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the oracle parity check")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the per-config / strong-scaling extra keys")
     ap.add_argument("--optimize-only", action="store_true", help="print only the optimize key (N = 1)")
     args = ap.parse_args()
 
@@ -480,7 +517,12 @@ def main():
         print(json.dumps({"optimize": {name: optimize_line(name, device=local_rank)
                                        for name in ("config4", "config3", "config2")}}))
         return
-    m = measure(ba, args.steps, args.warmup, args.ramp_seconds, KERNEL_WINDOW)
+    m = timed_steps(ba, args.steps, args.warmup, args.ramp_seconds)
+    ba.check()   # a failed step (peer timeout, not PD) stops the later ones: never report that as speed
+    if args.dump_outputs:
+        dump_outputs(ba, args.dump_outputs, rank, world)
+    if args.full:
+        m.update(kernel_timing(ba, KERNEL_WINDOW))
     st = ba.stats()
     kern = lin_kernels(ba)
     solve = ba.solve_stats()
@@ -490,17 +532,13 @@ def main():
     ba.close()
 
     strong = {}
-    if world > 1 and not args.no_extra:
+    if args.full and world > 1 and not args.no_extra:
         for name in ("config3", "config5"):
             strong[name] = strong_line(name, rank, world, local_rank, same_device)
 
     if rank != 0:
         return
-    tr = load_profile("traffic", args.config, views_per_rank) if world == 1 else None
     model = MODEL_NAMES[rig.CONFIGS[args.config]["model"]]
-    rl = roofline(st, m["lin_ms"], tr, kernel=kern)
-    rl["kernel_launches_timed"] = m["nlaunch"]
-    rl["step_ms_events"] = m["step_ms_ev"]
     out = {
         "metric": METRIC,
         "value": value,
@@ -526,10 +564,17 @@ def main():
             "state_dtype": "f32", "jacobian_dtype": "f64",
         },
         "clock_ramp": m["ramp"],
-        "step_distribution": m["dist"],
-        "exchange_ms": m["xchg_ms"] if world > 1 else None,
-        "roofline": rl,
     }
+    if solve["warm"] or solve["direct"]:
+        out["warm_solve"] = solve
+    if not args.full:
+        print(json.dumps(out))
+        return
+    tr = load_profile("traffic", args.config, views_per_rank) if world == 1 else None
+    rl = roofline(st, m["lin_ms"], tr, kernel=kern)
+    rl["kernel_launches_timed"] = m["nlaunch"]
+    rl["step_ms_events"] = m["step_ms_ev"]
+    out.update(step_distribution=m["dist"], exchange_ms=m["xchg_ms"] if world > 1 else None, roofline=rl)
     fp = load_profile("fp64", args.config, views_per_rank) if world == 1 else None
     if fp and fp.get("fp64_flops_per_launch"):
         tf = fp["fp64_flops_per_launch"] / (m["lin_ms"] * 1e-3) / 1e12
@@ -546,8 +591,6 @@ def main():
             out["fp64_valu"]["valu_issue_frac"] = {k: round(sq["kernels"][k]["valu_issue_frac"], 4) for k in ks}
             out["fp64_valu"]["valu_issue_source"] = ("profiles/sq_*.json: SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES "
                                                      "x waves per SIMD (tools/pmc_sq.sh)")
-    if solve["warm"] or solve["direct"]:
-        out["warm_solve"] = solve
     if strong:
         out["strong"] = strong
     if not args.no_parity and world == 1:

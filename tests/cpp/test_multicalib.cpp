@@ -2,8 +2,9 @@
 // cv::multicalib (samples/multi_cameras_calibration.cpp: construct, loadImages + initialize,
 // optimizeExtrinsics).  Built and run by tests/test_cpp_host.py:
 //
-//   test_multicalib selftest              host-only checks (no GPU): Rodrigues round trips,
-//                                         buildParas / paras2vertex layouts, error behaviour
+//   test_multicalib selftest [dir]        host-only checks (no GPU): Rodrigues round trips,
+//                                         buildParas / paras2vertex layouts, error behaviour;
+//                                         the FileStorage round trip writes into dir (default /tmp)
 //   test_multicalib run <in.bin> <out.txt>  fixture problem (written by the test from a golden
 //                                         npz): seam at x0, computeProjectError, optimizeExtrinsics
 //   test_multicalib storage <file>        FileStorage read: one line per top-level key
@@ -50,7 +51,7 @@ static double maxdiff(const std::vector<float>& a, const std::vector<float>& b) 
     return m;
 }
 
-static int selftest() {
+static int selftest(const std::string& dir) {
     // Rodrigues: vector -> matrix -> vector, including the small-angle and ~pi branches
     const float cases[][3] = {{0.1f, -0.2f, 0.3f}, {1e-9f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {3.1f, 0.05f, -0.02f},
                               {-0.7f, 1.2f, 0.4f}};
@@ -144,7 +145,7 @@ static int selftest() {
     }
     // FileStorage: write XML and YAML, read back every kind
     for (const char* ext : {".xml", ".yaml"}) {
-        const std::string fn = std::string("/tmp/mcc_storage_selftest") + ext;
+        const std::string fn = dir + "/mcc_storage_selftest" + ext;
         {
             mcc::storage::FileStorage fs(fn, mcc::storage::FileStorage::WRITE);
             fs.write("nCameras", 3);
@@ -273,7 +274,7 @@ static int run(const char* in, const char* outp) {
 
 int main(int argc, char** argv) {
     try {
-        if (argc >= 2 && !std::strcmp(argv[1], "selftest")) return selftest();
+        if (argc >= 2 && !std::strcmp(argv[1], "selftest")) return selftest(argc >= 3 ? argv[2] : "/tmp");
         if (argc >= 4 && !std::strcmp(argv[1], "run")) return run(argv[2], argv[3]);
         if (argc >= 3 && !std::strcmp(argv[1], "storage")) {
             mcc::storage::FileStorage fs(argv[2], mcc::storage::FileStorage::READ);

@@ -24,8 +24,9 @@ views of the reference's tutorials/data/omni_stereocalib_data.xml (2 omnidirecti
 cv::omnidir::calibrate (the oracle's restatement, TermCriteria(COUNT+EPS, 300, 1e-7)), one edge per
 calibrated view with the view pose as its transform, photo vertices by timestamp, the BFS pose
 chain from camera 0, then buildParas; optimised with the base class default TermCriteria
-(COUNT, 20, 1e-7) (multicalib.hpp:140).  The fixture carries the raw 20-view corner arrays too,
-so no GPU test reads /root/reference.
+(COUNT, 20, 1e-7) (multicalib.hpp:140).  The fixture carries the raw 20-view corner arrays too;
+the data file itself is kept as tests/golden/tutorial/omni_stereocalib_data.xml, so nothing
+here reads outside the repository.
 
 The oracle is the reference restated (parity against OpenCV itself is unpinned, see
 tests/test_oracle_math.py); these vectors freeze it so the GPU path and any later oracle change
@@ -45,7 +46,7 @@ from multi_camera_calibration_amd import rig  # noqa: E402
 from oracle import oracle_py as O  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-STEREO_XML = "/root/reference/tutorials/data/omni_stereocalib_data.xml"
+STEREO_XML = os.path.join(HERE, "tutorial", "omni_stereocalib_data.xml")   # a copy of the reference's data file
 
 
 # ---------------------------------------------------------------- the real-corner case

@@ -1,10 +1,11 @@
 """Generates the cv::omnidir::calibrate fixtures tests/golden/omnidir/*.npz.
 
-Run from the repo root (in the build container, where /root/reference is readable):
+Run from the repo root:
     python tests/golden/make_golden_omnidir.py
 
 Inputs:
   omni_calib_data ... the reference's own real corner data, tutorials/data/omni_calib_data.xml
+                      (kept as tests/golden/tutorial/omni_calib_data.xml)
                       (15 views of a 9x6 board, 1280x960; pattern points CV_64F, image points as
                       stored), the data tutorials/omnidir_tutorial.markdown:40-49 calibrates with
                       TermCriteria(COUNT + EPS, 200, 1e-4) and flags 0;
@@ -32,7 +33,7 @@ from multi_camera_calibration_amd import rig  # noqa: E402
 from oracle import oracle_py as O  # noqa: E402
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "omnidir")
-TUTORIAL = "/root/reference/tutorials/data/omni_calib_data.xml"
+TUTORIAL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tutorial", "omni_calib_data.xml")
 
 
 def read_opencv_mats(path, key):
@@ -73,8 +74,7 @@ def generate(off, obj, img, size, flags, crit):
 
 
 def cases():
-    if os.path.exists(TUTORIAL):
-        yield "omni_calib_data", tutorial_inputs(), 0, (3, 200, 1e-4)
+    yield "omni_calib_data", tutorial_inputs(), 0, (3, 200, 1e-4)
     s = rig.make_omni_views(16, seed=4)
     yield "synth_v16", (s.off, s.obj, s.img, s.image_size), 0, (3, 300, 1e-7)
     yield "synth_v16_fix", (s.off, s.obj, s.img, s.image_size), 2 + 16 + 32, (3, 300, 1e-7)

@@ -35,8 +35,8 @@ def exe(tmp_path_factory):
     return out
 
 
-def test_cpp_host_selftest(exe):
-    r = subprocess.run([exe, "selftest"], capture_output=True, text=True, timeout=60)
+def test_cpp_host_selftest(exe, tmp_path):
+    r = subprocess.run([exe, "selftest", str(tmp_path)], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "selftest ok" in r.stdout
 

@@ -19,7 +19,6 @@ import make_golden  # noqa: E402
 
 FIXTURES = sorted(glob.glob(os.path.join(HERE, "golden", "*.npz")))
 REGEN = make_golden.CASES
-REAL = {"tutorial_stereo_v20"}   # rebuilt from /root/reference/tutorials/data (skipped without it)
 
 
 def _name(path):
@@ -38,8 +37,6 @@ def test_fixture_set_complete():
 
 def test_generator_reproduces_inputs(fx):
     name, g, p = fx
-    if name in REAL and not os.path.exists(make_golden.STEREO_XML):
-        pytest.skip("the reference's tutorial data is not on this machine")
     q = REGEN[name]()
     if isinstance(q, tuple):
         q, extra = q

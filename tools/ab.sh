@@ -21,7 +21,7 @@ for i in $(seq 1 $N); do
       done
     fi
     [ -n "$STATS" ] && EE="$EE MCC_SOLVE_STATS=1"
-    env $EE timeout -k 10 150 python3 bench.py --config $CFG --no-cpu --no-parity --no-extra \
+    env $EE timeout -k 10 150 python3 bench.py --full --config $CFG --no-cpu --no-parity --no-extra \
         --steps ${STEPS:-2000} --warmup ${WARMUP:-100} > gpurun_out/ab.json 2>gpurun_out/ab.err || exit 1
     python3 -c "
 import json, sys

@@ -27,9 +27,9 @@ for s in $STEPS; do
         ok_rc $rc || exit 10
         ;;
     bench)
-        timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" || exit 11
+        timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" || exit 11
         echo "bench (driver settings):"; cut -c1-600 "$OUT/bench_driver.json"
-        timeout -k 10 400 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 12
+        timeout -k 10 400 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 12
         echo "bench (defaults):"; cut -c1-400 "$OUT/bench_default.json"
         ;;
     prof)
@@ -38,7 +38,7 @@ for s in $STEPS; do
         # hipGraphLaunch; tools/profile_r03.sh adds the PMC passes
         for cfg in config4 config2 config3 config5; do
             ( cd /tmp && export TMPDIR=/tmp && export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/stats_$cfg" -o run \
-                --output-format csv -- python3 "$R/bench.py" --config $cfg --steps 20 --warmup 5 --no-cpu --no-parity --no-extra \
+                --output-format csv -- python3 "$R/bench.py" --full --config $cfg --steps 20 --warmup 5 --no-cpu --no-parity --no-extra \
                 > "$OUT/prof_$cfg.json" 2> "$OUT/prof_$cfg.err" ) || exit 13
             f=$(find "$OUT/stats_$cfg" -name "*kernel_stats.csv" | head -n 1)
             [ -n "$f" ] && cp "$f" "$OUT/kernel_stats_$cfg.csv" && echo "== $cfg" && cut -c1-120 "$OUT/kernel_stats_$cfg.csv" | grep k_

@@ -8,7 +8,7 @@ n=0
 for L in "$@"; do
   n=$((n + 1))
   ( cd /tmp && export TMPDIR=/tmp && MCC_LIB=$R/$L timeout -s KILL 120 rocprofv3 --pmc SQC_ICACHE_MISSES SQC_ICACHE_HITS SQC_ICACHE_REQ SQ_WAVES \
-      -d $OUT/ic_$n -o run --output-format csv -- python3 $R/bench.py --config config4 --no-cpu --no-parity --no-extra \
+      -d $OUT/ic_$n -o run --output-format csv -- python3 $R/bench.py --full --config config4 --no-cpu --no-parity --no-extra \
       --steps 30 --warmup 4 --ramp-seconds 0.05 > $OUT/ic_$n.log 2>&1 ) || exit 1
   f=$(find $OUT/ic_$n -name "*counter_collection.csv" | head -n 1)
   python3 - "$f" "$L" <<'PY'

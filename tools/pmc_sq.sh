@@ -10,7 +10,7 @@ R=$PWD
 mkdir -p "$OUT"
 ( cd /tmp && export TMPDIR=/tmp && MCC_LIB=${LIB:+$R/$LIB} timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU \
     SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU -d "$OUT" -o run \
-    --output-format csv -- python3 "$R/bench.py" --config "$CFG" --no-cpu --no-parity --no-extra --steps 20 --warmup 4 \
+    --output-format csv -- python3 "$R/bench.py" --full --config "$CFG" --no-cpu --no-parity --no-extra --steps 20 --warmup 4 \
     > "$OUT/bench.json" 2> "$OUT/bench.err" ) || exit 1
 python3 - "$OUT" "$CFG" "$JS" "$VIEWS" <<'PY'
 import csv, glob, json, sys

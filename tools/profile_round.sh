@@ -23,7 +23,7 @@ if [ "$1" = "final" ]; then
     rc=$?; grep -E "FAILED|ERROR|passed|failed" $OUT/pytest.log | tail -20; [ $rc -eq 0 ] || exit 10
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit 11
     tail -1 $OUT/smoke.log
-    timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 12
+    timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 12
     tail -c 1500 $OUT/bench.json
 fi
 STEPS=${*:-config4 config2 config3 config5}
@@ -37,7 +37,7 @@ for cfg in $STEPS; do
     config5) ST=200; WU=20; PS=20; VIEWS=2000 ;;
     *) echo "unknown config $cfg"; exit 30 ;;
     esac
-    B="$R/bench.py --config $cfg --no-cpu --no-parity --no-extra"
+    B="$R/bench.py --full --config $cfg --no-cpu --no-parity --no-extra"
     ( cd /tmp && export TMPDIR=/tmp &&
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/${cfg}_stats" -o run --output-format csv \
           -- python3 $B --steps $ST --warmup $WU > "$OUT/${cfg}_stats.log" 2>&1 ) || exit 31

@@ -23,7 +23,7 @@ for s in "$@"; do
       WU=100; [ "$st" -le 50 ] && WU=5
       ROUNDS=${ROUNDS:-3} STEPS=$st WARMUP=$WU tools/ab.sh $cfg "lib=build_ab/r05head/libmcc.so" "-" | tee -a $OUT/ab.txt || exit 11 ;;
     opt)
-      timeout -k 10 300 python bench.py --optimize-only > $OUT/opt.json 2> $OUT/opt.err || exit 12
+      timeout -k 10 300 python bench.py --full --optimize-only > $OUT/opt.json 2> $OUT/opt.err || exit 12
       python3 -c "
 import json; d=json.load(open('$OUT/opt.json'))['optimize']
 for k,v in d.items(): print(k, v['iterations'], 'iters; wall', round(v['wall_ms_per_call'],3), 'ms; device', round(v['device_ms_per_call'],3), 'ms,', round(v['device_ms_per_iteration']*1e3,1), 'us/iter; host', {a: round(b,3) for a,b in v['host_ms'].items()}, v['solves_per_call'], 'by count', [round(x*1e3,1) for x in v['device_ms_by_count']['device_ms']])

@@ -9,7 +9,7 @@ MCC_DIAG_RT=1 MCC_LIB=multi_camera_calibration_amd/libmcc_diagrt.so timeout -k 1
     python tools/diag_schur.py config4 > "$OUT/schur4rt.txt" 2>&1 || exit 10
 cat "$OUT/schur4rt.txt"
 MCC_BENCH_SAME_DEVICE=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 \
+    --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 5 \
     > "$OUT/bench_n2.json" 2> "$OUT/bench_n2.err" || exit 11
 python3 -c "
 import json; d=json.loads(open('$OUT/bench_n2.json').read().strip().split('\n')[-1])
