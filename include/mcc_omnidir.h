@@ -1,6 +1,7 @@
 /*
  * mcc_omnidir.h -- C ABI of the MI355X per-camera intrinsic calibration of the Mei omnidirectional
- * model (libmcc.so): cv::omnidir::calibrate, SURVEY.md 8(f) row 4.
+ * model (libmcc.so): cv::omnidir::calibrate, SURVEY.md 8(f) row 4, and of the joint calibration of
+ * a two-camera rig, cv::omnidir::stereoCalibrate (second half of this header).
  *
  * The reference calls it once per camera from MultiCameraCalibration::loadImages
  * (src/multicalib.cpp:273-278, TermCriteria(COUNT + EPS, 300, 1e-7)) before the extrinsic
@@ -18,6 +19,18 @@
  *                                 and one G of the loop (src/omnidir.cpp:1134-1142).
  *   mcc_omnicalib_optimize ...... the loop of calibrate (src/omnidir.cpp:1126-1149), on the device.
  *   mcc_omnicalib_rms ........... estimateUncertainties' rms (src/omnidir.cpp:1791-1803).
+ *   mcc_omnidir_stereo_calibrate  cv::omnidir::stereoCalibrate (src/omnidir.cpp:1213-1381).
+ *   mcc_omnidir_stereo_initialize cv::omnidir::internal::initializeStereoCalibration (:750-846).
+ *   mcc_omnidir_stereo_encode_init  its host part: getInterset (:2229-2268), the relative poses
+ *                                 (:786-797), findMedian3 (:2172-2188), encodeParametersStereo
+ *                                 (:1570-1619); no GPU.
+ *   mcc_omnistereo_create ....... the per-view point lists stereoCalibrate converts to CV_64F
+ *                                 (:1227-1238), deep-copied to the device.
+ *   mcc_omnistereo_jacobian ..... cv::omnidir::internal::computeJacobianStereo (:937-1020) with
+ *                                 compose_motion (:1023-1065), flags2idxStereo / fillFixedStereo
+ *                                 (:2078-2170), and one G of the loop (:1280-1290).
+ *   mcc_omnistereo_optimize ..... the loop of stereoCalibrate (:1274-1301), on the device.
+ *   mcc_omnistereo_rms .......... estimateUncertaintiesStereo's rms (:1826-1888).
  *
  * Parameters use the reference's encodeParameters layout (src/omnidir.cpp:1541-1568), CV_64F:
  *   x = [om_0(3), T_0(3), ..., om_{n-1}, T_{n-1}, fx, fy, s, cx, cy, xi, k1, k2, p1, p2], P = 6n + 10.
@@ -90,6 +103,83 @@ int mcc_omnidir_calibrate(int n_views, const int *view_off, const double *obj, c
                           int height, int flags, int crit_type, int max_count, double eps, int device, double *K,
                           double *xi, double *D, double *om, double *t, int *idx, int *n_idx, double *rms,
                           int *iters);
+
+/* ---------------------------------------------------------------- cv::omnidir::stereoCalibrate
+ * Two Mei cameras that see the same pattern views.  Parameters use the reference's
+ * encodeParametersStereo layout, CV_64F, P = 6 (n + 1) + 20:
+ *   x = [om(3), T(3), omL_0, tL_0, ..., omL_{n-1}, tL_{n-1}, intr_1(10), intr_2(10)],
+ *   intr = fx, fy, s, cx, cy, xi, k1, k2, p1, p2.
+ * (om, T) maps the left-camera frame to the right-camera frame: the right camera's pose of view i
+ * is compose_motion(omL_i, tL_i, om, T), R2 = R(om) R(omL_i), T2 = R(om) tL_i + T.
+ *
+ * Every view must hold the same number of points (computeJacobianStereo takes n_points from view
+ * 0, src/omnidir.cpp:947), at least 3 and at most 2048; anything else is MCC_EINVAL before any
+ * device work.  The step kernel walks a view's corners in chunks of 64 or 128 and keeps the Gram in
+ * the matrix-core accumulators, so LDS does not bound the corner count; 2048 is an argument check.
+ *
+ * MCC_OMNI_CALIB_USE_GUESS is handled as the single-camera path handles it: the bit is accepted
+ * and ignored.  flags2idxStereo does not look at it, the initialisation always runs, and K / xi /
+ * D are outputs only.  The FIX_* flags apply to both cameras' intrinsics; (om, T) and the kept
+ * poses are never fixed.  A view whose 6 x 6 pose block is not positive definite fails with
+ * MCC_ENOTPD (the reference propagates NaN).  estimateUncertaintiesStereo's `errors` are not
+ * computed. */
+typedef struct mcc_omnistereo mcc_omnistereo;
+
+typedef struct mcc_omnistereo_desc {
+    int n_views;
+    const int *view_off;   /* [n_views + 1] corner ranges, all of the same length */
+    const double *obj;     /* [3 * corners] pattern points (x, y, z)             */
+    const double *img1;    /* [2 * corners] image points of camera 1 (left)      */
+    const double *img2;    /* [2 * corners] image points of camera 2 (right)     */
+    int flags;             /* MCC_OMNI_CALIB_FIX_* (flags2idxStereo semantics)   */
+    int device;            /* HIP device ordinal                                 */
+} mcc_omnistereo_desc;
+
+int mcc_omnistereo_create(mcc_omnistereo **out, const mcc_omnistereo_desc *desc);
+void mcc_omnistereo_destroy(mcc_omnistereo *h);
+int mcc_omnistereo_nparams(const mcc_omnistereo *h);
+
+/* computeJacobianStereo at params (P) for loop iteration iter: jte[P] = J^T E before the flag
+ * reduction, G[P] = alpha_smooth2 (JTJ + epsilon)^-1 JTE with fixed entries 0 (fillFixedStereo).
+ * Either output may be NULL. */
+int mcc_omnistereo_jacobian(mcc_omnistereo *h, const double *params, int iter, double *jte, double *G);
+
+/* stereoCalibrate's loop from params_inout (P): crit_type MCC_CRIT_COUNT / EPS / COUNT_EPS. */
+int mcc_omnistereo_optimize(mcc_omnistereo *h, int crit_type, int max_count, double eps, double *params_inout,
+                            int *iters, double *last_change);
+
+/* rms reprojection error over both cameras' points at params (estimateUncertaintiesStereo) */
+int mcc_omnistereo_rms(mcc_omnistereo *h, const double *params, double *rms);
+
+/* measurement, as mcc_omnicalib_time_steps: n_steps unconditional loop steps, graph-launched. */
+int mcc_omnistereo_time_steps(mcc_omnistereo *h, const double *params, int n_steps, double *ms_per_step);
+
+/* The host part of initializeStereoCalibration after its two calibrate calls (no GPU): the
+ * intersection of the two kept lists idx1[n1] / idx2[n2] in the first list's order (getInterset),
+ * per common view the relative pose R2 R1^T, T2 - R2 R1^T T1 of the two cameras' poses
+ * (om1 / t1 [3 * n1], om2 / t2 [3 * n2], in kept order), the reference's median of each component
+ * (findMedian: an even count gives the upper-middle element, an odd count the mean of the middle
+ * element and the one below it), and encodeParametersStereo with the first camera's poses.
+ * params must hold 6 (min(n1, n2) + 1) + 20 doubles, idx min(n1, n2) ints. */
+int mcc_omnidir_stereo_encode_init(int n1, const int *idx1, const double *om1, const double *t1, int n2,
+                                   const int *idx2, const double *om2, const double *t2, const double *K1, double xi1,
+                                   const double *D1, const double *K2, double xi2, const double *D2, double *params,
+                                   int *idx, int *n_idx);
+
+/* initializeStereoCalibration: two mcc_omnidir_calibrate runs with TermCriteria(3, 100, 1e-6) and
+ * the caller's flags (on the GPU), then mcc_omnidir_stereo_encode_init.  params must hold
+ * 6 (n_views + 1) + 20 doubles (6 (n_idx + 1) + 20 are written), idx n_views ints. */
+int mcc_omnidir_stereo_initialize(int n_views, const int *view_off, const double *obj, const double *img1,
+                                  const double *img2, int width1, int height1, int width2, int height2, int flags,
+                                  int device, double *params, int *idx, int *n_idx);
+
+/* cv::omnidir::stereoCalibrate: K1 / K2 [9], xi1 / xi2, D1 / D2 [4], om[3], T[3], omL / tL
+ * [3 * n_views] (kept views), idx, n_idx, rms, iterations (may be NULL). */
+int mcc_omnidir_stereo_calibrate(int n_views, const int *view_off, const double *obj, const double *img1,
+                                 const double *img2, int width1, int height1, int width2, int height2, int flags,
+                                 int crit_type, int max_count, double eps, int device, double *K1, double *xi1,
+                                 double *D1, double *K2, double *xi2, double *D2, double *om, double *T, double *omL,
+                                 double *tL, int *idx, int *n_idx, double *rms, int *iters);
 
 #ifdef __cplusplus
 }

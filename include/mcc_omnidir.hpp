@@ -1,5 +1,6 @@
 /*
- * mcc_omnidir.hpp -- C++ mirror of cv::omnidir::calibrate over the C ABI (mcc_omnidir.h):
+ * mcc_omnidir.hpp -- C++ mirror of cv::omnidir::calibrate and cv::omnidir::stereoCalibrate (below)
+ * over the C ABI (mcc_omnidir.h):
  * the same name, argument order and meaning as include/opencv2/ccalib/omnidir.hpp's
  *
  *   double calibrate(InputArrayOfArrays objectPoints, InputArrayOfArrays imagePoints, Size size,
@@ -77,6 +78,69 @@ inline double calibrate(const std::vector<std::vector<Vec3d>>& objectPoints,
         for (int k = 0; k < 3; ++k) {
             rvecs[i][k] = om[3 * i + k];
             tvecs[i][k] = t[3 * i + k];
+        }
+    if (idx) idx->assign(kept.begin(), kept.begin() + nk);
+    return rms;
+}
+
+/*
+ * cv::omnidir::stereoCalibrate (src/omnidir.cpp:1213-1381), the same name, argument order and meaning as
+ *
+ *   double stereoCalibrate(InputOutputArrayOfArrays objectPoints, InputOutputArrayOfArrays imagePoints1,
+ *                          InputOutputArrayOfArrays imagePoints2, const Size& imageSize1, const Size& imageSize2,
+ *                          InputOutputArray K1, InputOutputArray xi1, InputOutputArray D1, InputOutputArray K2,
+ *                          InputOutputArray xi2, InputOutputArray D2, OutputArray rvec, OutputArray tvec,
+ *                          OutputArrayOfArrays rvecsL, OutputArrayOfArrays tvecsL, int flags,
+ *                          TermCriteria criteria, OutputArray idx = noArray());
+ *
+ * (rvec, tvec) maps the first camera's frame to the second's; rvecsL / tvecsL are the first camera's
+ * poses of the kept views.  Every view needs the same number of points (std::invalid_argument
+ * otherwise); CALIB_USE_GUESS is accepted and ignored, as in calibrate.
+ */
+inline double stereoCalibrate(const std::vector<std::vector<Vec3d>>& objectPoints,
+                              const std::vector<std::vector<Vec2d>>& imagePoints1,
+                              const std::vector<std::vector<Vec2d>>& imagePoints2, Size imageSize1, Size imageSize2,
+                              std::array<double, 9>& K1, double& xi1, std::array<double, 4>& D1,
+                              std::array<double, 9>& K2, double& xi2, std::array<double, 4>& D2, Vec3d& rvec,
+                              Vec3d& tvec, std::vector<Vec3d>& rvecsL, std::vector<Vec3d>& tvecsL, int flags,
+                              TermCriteria criteria, std::vector<int>* idx = nullptr, int device = 0) {
+    if (objectPoints.empty() || objectPoints.size() != imagePoints1.size() || objectPoints.size() != imagePoints2.size())
+        throw std::invalid_argument("omnidir::stereoCalibrate: objectPoints, imagePoints1 and imagePoints2 must be "
+                                    "non-empty and of equal count");
+    const int n = (int)objectPoints.size();
+    const size_t np = objectPoints[0].size();
+    std::vector<int> off(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        if (objectPoints[i].size() != np || imagePoints1[i].size() != np || imagePoints2[i].size() != np)
+            throw std::invalid_argument("omnidir::stereoCalibrate: view " + std::to_string(i) +
+                                        " does not hold the point count of view 0 in all three lists");
+        off[i + 1] = off[i] + (int)np;
+    }
+    std::vector<double> obj(3 * (size_t)off[n]), img1(2 * (size_t)off[n]), img2(2 * (size_t)off[n]);
+    for (int i = 0; i < n; ++i)
+        for (size_t j = 0; j < np; ++j) {
+            for (int k = 0; k < 3; ++k) obj[3 * (off[i] + j) + k] = objectPoints[i][j][k];
+            for (int k = 0; k < 2; ++k) {
+                img1[2 * (off[i] + j) + k] = imagePoints1[i][j][k];
+                img2[2 * (off[i] + j) + k] = imagePoints2[i][j][k];
+            }
+        }
+    std::vector<double> om(3 * (size_t)n), t(3 * (size_t)n);
+    std::vector<int> kept(n);
+    int nk = 0, iters = 0;
+    double rms = 0;
+    const int rc = mcc_omnidir_stereo_calibrate(n, off.data(), obj.data(), img1.data(), img2.data(), imageSize1.width,
+                                                imageSize1.height, imageSize2.width, imageSize2.height, flags,
+                                                criteria.type, criteria.maxCount, criteria.epsilon, device, K1.data(),
+                                                &xi1, D1.data(), K2.data(), &xi2, D2.data(), rvec.data(), tvec.data(),
+                                                om.data(), t.data(), kept.data(), &nk, &rms, &iters);
+    if (rc != MCC_OK) throw std::runtime_error(std::string("omnidir::stereoCalibrate: ") + mcc_last_error());
+    rvecsL.assign(nk, Vec3d{});
+    tvecsL.assign(nk, Vec3d{});
+    for (int i = 0; i < nk; ++i)
+        for (int k = 0; k < 3; ++k) {
+            rvecsL[i][k] = om[3 * i + k];
+            tvecsL[i][k] = t[3 * i + k];
         }
     if (idx) idx->assign(kept.begin(), kept.begin() + nk);
     return rms;

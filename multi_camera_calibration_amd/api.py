@@ -51,12 +51,18 @@ class _OmniDesc(ctypes.Structure):
                 ("flags", ctypes.c_int), ("device", ctypes.c_int)]
 
 
+class _OmniStereoDesc(ctypes.Structure):
+    _fields_ = [("n_views", ctypes.c_int), ("view_off", _i32p), ("obj", _f64p), ("img1", _f64p), ("img2", _f64p),
+                ("flags", ctypes.c_int), ("device", ctypes.c_int)]
+
+
 _LIB = None
 
 
 HOST_LIB_PATH = os.path.join(_HERE, "libmcc_host.so")
 SAMPLE_PATH = os.path.join(_HERE, "build", "multi_cameras_calibration")
 OMNI_SAMPLE_PATH = os.path.join(_HERE, "build", "omni_calibration")
+OMNI_STEREO_SAMPLE_PATH = os.path.join(_HERE, "build", "omni_stereo_calibration")
 # the reference's samples/multi_cameras_calibration.cpp compiled unchanged against
 # include/opencv2/ccalib/*.hpp (built only where the reference tree exists; the binary travels)
 REF_SAMPLE_SRC = "/root/reference/samples/multi_cameras_calibration.cpp"
@@ -69,7 +75,7 @@ def build(force: bool = False) -> str:
     inc = os.path.dirname(HEADER)
     srcs = [os.path.join(_HERE, d, f) for d in ("csrc", "host", "samples") for f in os.listdir(os.path.join(_HERE, d))]
     srcs += [os.path.join(inc, f) for f in os.listdir(inc)]
-    outs = [LIB_PATH, HOST_LIB_PATH, SAMPLE_PATH, OMNI_SAMPLE_PATH]
+    outs = [LIB_PATH, HOST_LIB_PATH, SAMPLE_PATH, OMNI_SAMPLE_PATH, OMNI_STEREO_SAMPLE_PATH]
     stale = any(not os.path.exists(o) for o in outs) or any(
         os.path.getmtime(s) > min(os.path.getmtime(o) for o in outs) for s in srcs)
     if force or stale:
@@ -149,6 +155,22 @@ def lib():
         L.mcc_omnidir_calibrate.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                             _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p, _f64p, _i32p]
+        L.mcc_omnistereo_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_OmniStereoDesc)]
+        L.mcc_omnistereo_destroy.argtypes = [ctypes.c_void_p]
+        L.mcc_omnistereo_destroy.restype = None
+        L.mcc_omnistereo_nparams.argtypes = [ctypes.c_void_p]
+        L.mcc_omnistereo_jacobian.argtypes = [ctypes.c_void_p, _f64p, ctypes.c_int, _f64p, _f64p]
+        L.mcc_omnistereo_optimize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, _f64p,
+                                              _i32p, _f64p]
+        L.mcc_omnistereo_rms.argtypes = [ctypes.c_void_p, _f64p, _f64p]
+        L.mcc_omnistereo_time_steps.argtypes = [ctypes.c_void_p, _f64p, ctypes.c_int, _f64p]
+        L.mcc_omnidir_stereo_encode_init.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, ctypes.c_int, _i32p, _f64p,
+                                                     _f64p, _f64p, ctypes.c_double, _f64p, _f64p, ctypes.c_double,
+                                                     _f64p, _f64p, _i32p, _i32p]
+        L.mcc_omnidir_stereo_initialize.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, _f64p] + [ctypes.c_int] * 6 + [
+            _f64p, _i32p, _i32p]
+        L.mcc_omnidir_stereo_calibrate.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, _f64p] + [ctypes.c_int] * 7 + [
+            ctypes.c_double, ctypes.c_int] + [_f64p] * 10 + [_i32p, _i32p, _f64p, _i32p]
         _LIB = L
     return _LIB
 
@@ -568,3 +590,132 @@ def omnidir_calibrate(off, obj, img, image_size, flags=0, crit_type=MCC_CRIT_COU
            "mcc_omnidir_calibrate")
     k = nk.value
     return rms.value, K.reshape(3, 3), xi.value, D, om[:k], t[:k], idx[:k].copy(), it.value
+
+
+# ---------------------------------------------------------------- cv::omnidir::stereoCalibrate
+# include/mcc_omnidir.h; the reference's names: cv::omnidir::stereoCalibrate (src/omnidir.cpp:1213-1381),
+# internal::initializeStereoCalibration (:750-846), internal::computeJacobianStereo (:937-1020).
+def _stereo_views(off, obj, img1, img2):
+    off, obj, img1 = _views(off, obj, img1)
+    img2 = np.ascontiguousarray(img2, np.float64).reshape(-1, 2)
+    if img2.shape[0] != img1.shape[0]:
+        raise MccError("view offsets / points mismatch")
+    return off, obj, img1, img2
+
+
+class OmniStereoCalibrator:
+    """The device-resident state of cv::omnidir::stereoCalibrate's loop for the views both cameras
+    see (CV_64F points, the same corner count in every view; parameters in encodeParametersStereo
+    layout, P = 6(n + 1) + 20)."""
+
+    def __init__(self, off, obj, img1, img2, flags: int = 0, device: int = 0):
+        self.off, self.obj, self.img1, self.img2 = _stereo_views(off, obj, img1, img2)
+        d = _OmniStereoDesc()
+        d.n_views = self.off.size - 1
+        d.view_off = _ptr(self.off, _i32p)
+        d.obj = _ptr(self.obj, _f64p)
+        d.img1 = _ptr(self.img1, _f64p)
+        d.img2 = _ptr(self.img2, _f64p)
+        d.flags, d.device = flags, device
+        h = ctypes.c_void_p()
+        _check(lib().mcc_omnistereo_create(ctypes.byref(h), ctypes.byref(d)), "mcc_omnistereo_create")
+        self.h = h
+        self.P = lib().mcc_omnistereo_nparams(h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcc_omnistereo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def compute_jacobian(self, params, it=0):
+        """(JTE before the flag reduction, G of loop iteration `it`) at params (computeJacobianStereo)."""
+        p = np.ascontiguousarray(params, np.float64)
+        jte, G = np.zeros(self.P), np.zeros(self.P)
+        _check(lib().mcc_omnistereo_jacobian(self.h, _ptr(p, _f64p), it, _ptr(jte, _f64p), _ptr(G, _f64p)),
+               "mcc_omnistereo_jacobian")
+        return jte, G
+
+    def optimize(self, params, crit_type=MCC_CRIT_COUNT_EPS, max_count=200, eps=1e-4):
+        """stereoCalibrate's loop: (params, iterations, last change)."""
+        p = np.array(params, np.float64, copy=True)
+        it, ch = ctypes.c_int(0), ctypes.c_double(0)
+        _check(lib().mcc_omnistereo_optimize(self.h, crit_type, max_count, eps, _ptr(p, _f64p), ctypes.byref(it),
+                                             ctypes.byref(ch)), "mcc_omnistereo_optimize")
+        return p, it.value, ch.value
+
+    def rms(self, params):
+        p = np.ascontiguousarray(params, np.float64)
+        r = ctypes.c_double(0)
+        _check(lib().mcc_omnistereo_rms(self.h, _ptr(p, _f64p), ctypes.byref(r)), "mcc_omnistereo_rms")
+        return r.value
+
+    def time_steps(self, params, n_steps):
+        p = np.ascontiguousarray(params, np.float64)
+        ms = ctypes.c_double(0)
+        _check(lib().mcc_omnistereo_time_steps(self.h, _ptr(p, _f64p), n_steps, ctypes.byref(ms)),
+               "mcc_omnistereo_time_steps")
+        return ms.value
+
+
+def omnidir_stereo_encode_init(idx1, om1, t1, idx2, om2, t2, K1, xi1, D1, K2, xi2, D2):
+    """The host part of initializeStereoCalibration from the two cameras' calibrate results (kept
+    indices, poses in kept order, intrinsics): (params, idx of the common views) -- no GPU."""
+    idx1, idx2 = np.ascontiguousarray(idx1, np.int32), np.ascontiguousarray(idx2, np.int32)
+    a = [np.ascontiguousarray(v, np.float64) for v in (om1, t1, om2, t2, K1, D1, K2, D2)]
+    if a[0].size != 3 * idx1.size or a[1].size != 3 * idx1.size or a[2].size != 3 * idx2.size or \
+            a[3].size != 3 * idx2.size or a[4].size != 9 or a[6].size != 9 or a[5].size != 4 or a[7].size != 4:
+        raise MccError("kept lists / poses / intrinsics mismatch")
+    m = max(min(idx1.size, idx2.size), 1)
+    params, idx, nk = np.zeros(6 * (m + 1) + 20), np.zeros(m, np.int32), ctypes.c_int(0)
+    _check(lib().mcc_omnidir_stereo_encode_init(idx1.size, _ptr(idx1, _i32p), _ptr(a[0], _f64p), _ptr(a[1], _f64p),
+                                                idx2.size, _ptr(idx2, _i32p), _ptr(a[2], _f64p), _ptr(a[3], _f64p),
+                                                _ptr(a[4], _f64p), float(xi1), _ptr(a[5], _f64p), _ptr(a[6], _f64p),
+                                                float(xi2), _ptr(a[7], _f64p), _ptr(params, _f64p), _ptr(idx, _i32p),
+                                                ctypes.byref(nk)), "mcc_omnidir_stereo_encode_init")
+    k = nk.value
+    return params[:6 * (k + 1) + 20].copy(), idx[:k].copy()
+
+
+def omnidir_stereo_initialize(off, obj, img1, img2, image_size1, image_size2, flags=0, device=0):
+    """initializeStereoCalibration: (params in encodeParametersStereo layout, idx of the kept views);
+    the two single-camera calibrations run on the GPU."""
+    off, obj, img1, img2 = _stereo_views(off, obj, img1, img2)
+    n = off.size - 1
+    params, idx, nk = np.zeros(6 * (n + 1) + 20), np.zeros(n, np.int32), ctypes.c_int(0)
+    _check(lib().mcc_omnidir_stereo_initialize(n, _ptr(off, _i32p), _ptr(obj, _f64p), _ptr(img1, _f64p),
+                                               _ptr(img2, _f64p), int(image_size1[0]), int(image_size1[1]),
+                                               int(image_size2[0]), int(image_size2[1]), flags, device,
+                                               _ptr(params, _f64p), _ptr(idx, _i32p), ctypes.byref(nk)),
+           "mcc_omnidir_stereo_initialize")
+    k = nk.value
+    return params[:6 * (k + 1) + 20].copy(), idx[:k].copy()
+
+
+def omnidir_stereo_calibrate(off, obj, img1, img2, image_size1, image_size2, flags=0, crit_type=MCC_CRIT_COUNT_EPS,
+                             max_count=200, eps=1e-4, device=0):
+    """cv::omnidir::stereoCalibrate:
+    (rms, K1, xi1, D1, K2, xi2, D2, om, T, omL[k, 3], tL[k, 3], idx[k], iterations)."""
+    off, obj, img1, img2 = _stereo_views(off, obj, img1, img2)
+    n = off.size - 1
+    K1, K2, D1, D2, om, T = np.zeros(9), np.zeros(9), np.zeros(4), np.zeros(4), np.zeros(3), np.zeros(3)
+    omL, tL = np.zeros((n, 3)), np.zeros((n, 3))
+    xi1, xi2, rms = np.zeros(1), np.zeros(1), ctypes.c_double(0)
+    nk, it = ctypes.c_int(0), ctypes.c_int(0)
+    idx = np.zeros(n, np.int32)
+    _check(lib().mcc_omnidir_stereo_calibrate(n, _ptr(off, _i32p), _ptr(obj, _f64p), _ptr(img1, _f64p),
+                                              _ptr(img2, _f64p), int(image_size1[0]), int(image_size1[1]),
+                                              int(image_size2[0]), int(image_size2[1]), flags, crit_type, max_count,
+                                              eps, device, _ptr(K1, _f64p), _ptr(xi1, _f64p), _ptr(D1, _f64p),
+                                              _ptr(K2, _f64p), _ptr(xi2, _f64p), _ptr(D2, _f64p), _ptr(om, _f64p),
+                                              _ptr(T, _f64p), _ptr(omL, _f64p), _ptr(tL, _f64p), _ptr(idx, _i32p),
+                                              ctypes.byref(nk), ctypes.byref(rms), ctypes.byref(it)),
+           "mcc_omnidir_stereo_calibrate")
+    k = nk.value
+    return (rms.value, K1.reshape(3, 3), float(xi1[0]), D1, K2.reshape(3, 3), float(xi2[0]), D2, om, T, omL[:k],
+            tL[:k], idx[:k].copy(), it.value)

@@ -533,3 +533,76 @@ def make_omni_views(n_views=1000, board=(11, 8), square=40.0, seed=4, noise_px=0
     off = np.arange(n + 1, dtype=np.int32) * len(pts)
     return OmniCalibViews(off, np.tile(pts, (n, 1)), np.concatenate(imgs), (W, H), K, xi, D,
                           np.array(oms), np.array(ts))
+
+
+# ----------------------------------------------------------------------------- omni stereo views
+@dataclasses.dataclass
+class OmniStereoViews:
+    """Two omnidirectional cameras' corners of the same board views, as cv::omnidir::stereoCalibrate
+    takes them (src/omnidir.cpp:1213-1238): view i holds corners off[i]..off[i+1] of obj, img1
+    (camera 1, left) and img2 (camera 2, right).  (om, T) maps the left-camera frame to the right
+    one: the right camera sees view i at R(om) R(omL_i), R(om) tL_i + T."""
+    off: np.ndarray           # int32 [n+1]
+    obj: np.ndarray           # float64 [corners, 3]
+    img1: np.ndarray          # float64 [corners, 2]
+    img2: np.ndarray
+    image_size1: tuple        # (width, height)
+    image_size2: tuple
+    K1: np.ndarray            # truth (information only)
+    xi1: float
+    D1: np.ndarray
+    K2: np.ndarray
+    xi2: float
+    D2: np.ndarray
+    om: np.ndarray            # [3]
+    T: np.ndarray             # [3] mm
+    omL: np.ndarray           # [n, 3]
+    tL: np.ndarray            # [n, 3]
+
+    @property
+    def n_views(self) -> int:
+        return len(self.off) - 1
+
+
+def make_omni_stereo_views(n_views=16, board=(11, 8), square=40.0, seed=4, noise_px=0.2, size=(1280, 960),
+                           om=(0.02, -0.15, 0.03), T=(-120.0, 5.0, 8.0)) -> OmniStereoViews:
+    """A synthetic two-camera Mei rig: the left views are make_omni_views' (same seed, noise
+    included); the right camera is a second Mei camera (its own config-4 intrinsics) at the relative
+    pose (om, T).  Only views whose right-image corners all lie inside the image with the 20 px
+    margin are kept, the first n_views of them; the right corners get noise_px Gaussian noise."""
+    rng = np.random.default_rng(seed + 7919)
+    W, H = size
+    f = 350.0 * rng.uniform(0.97, 1.03)
+    K2 = np.array([[f, 0.0, W / 2 + rng.uniform(-10, 10)], [0, f * rng.uniform(0.99, 1.01), H / 2 + rng.uniform(-10, 10)],
+                   [0, 0, 1]])
+    xi2 = float(rng.uniform(0.8, 1.2))
+    D2 = np.array([rng.uniform(-0.1, 0.0), rng.uniform(0.0, 0.05), rng.uniform(-5e-4, 5e-4), rng.uniform(-5e-4, 5e-4)])
+    om, T = np.asarray(om, np.float64), np.asarray(T, np.float64)
+    R = rodrigues(om)
+    margin = 20.0
+    m = 2 * n_views + 8
+    while True:
+        left = make_omni_views(m, board=board, square=square, seed=seed, noise_px=noise_px, size=size)
+        keep, imgs2 = [], []
+        for i in range(left.n_views):
+            pts = left.obj[left.off[i]:left.off[i + 1]]
+            Xc = (pts @ rodrigues(left.om[i]).T + left.t[i]) @ R.T + T
+            if np.any(Xc[:, 2] < 50.0):
+                continue
+            uv = project_omni(Xc, K2, xi2, D2)
+            if np.any(uv[:, 0] < margin) or np.any(uv[:, 0] > W - margin) or np.any(uv[:, 1] < margin) \
+                    or np.any(uv[:, 1] > H - margin):
+                continue
+            keep.append(i)
+            imgs2.append(uv)
+        if len(keep) >= n_views:
+            break
+        m *= 2
+    keep, imgs2 = keep[:n_views], imgs2[:n_views]
+    N = int(left.off[1])
+    sel = np.concatenate([np.arange(left.off[i], left.off[i + 1]) for i in keep])
+    img2 = np.concatenate(imgs2)
+    img2 = img2 + rng.normal(scale=noise_px, size=img2.shape)
+    off = np.arange(n_views + 1, dtype=np.int32) * N
+    return OmniStereoViews(off, left.obj[sel], left.img[sel], img2, (W, H), (W, H), left.K, left.xi, left.D, K2, xi2,
+                           D2, om, T, left.om[keep], left.t[keep])
