@@ -203,6 +203,8 @@ struct mcc_problem {
     DevBuf<int> ssinv_ok;
     DevBuf<int> photo_ptr, photo_corner, edge_gblock, block_items, edge_photo, counter, cnt, cnt_blk;
     DevBuf<int> pgrp_ptr, pgrp_edge, gpair_ptr, gcon_ptr;
+    DevBuf<int> ghdr;        // k_group's per-group headers [n_pgroups][kGHdrInts] (LinArgs::ghdr)
+    DevBuf<double> kintr;    // the cameras' intrinsics rows in FP64 [C][kGIntr] (LinArgs::kintr)
     DevBuf<int> prep_ptr, prep_edge;   // k_prep4's groups (three-kernel split step)
     // MCC_POISON_HANDOFF=1 (test): every buffer handed between workgroups inside one launch or
     // between the step's kernels is filled with NaN (all-ones bytes) before each step, so that a
@@ -389,6 +391,7 @@ int enqueue_step(mcc_problem* p, int do_update, float* resid_dev, bool lin_only 
     la.Y = p->Y.p; la.zp = p->zp.p;
     la.pgrp_ptr = p->pgrp_ptr.p; la.pgrp_edge = p->pgrp_edge.p; la.edge_lphoto = p->edge_lphoto.p; la.gpair_ptr = p->gpair_ptr.p; la.gpairs = p->gpairs.p;
     la.gcon_ptr = p->gcon_ptr.p; la.gcon = p->gcon.p; la.pairprod = p->pairprod.p;
+    la.ghdr = p->ghdr.p; la.kintr = p->kintr.p;
     la.prep_ptr = p->prep_ptr.p; la.prep_edge = p->prep_edge.p; la.n_prep = p->n_prep; la.prep_lanes = p->prep_lanes;
     la.n_pgroups = p->n_pgroups; la.max_gpairs = p->max_gpairs; la.max_gcon = p->max_gcon; la.max_gedges = p->max_gedges;
     la.gp_tot = p->gp_tot.p;
@@ -1096,6 +1099,37 @@ int mcc_create(mcc_problem** out, const mcc_desc* d) {
             for (int v = pgrp_ptr[g]; v < pgrp_ptr[g + 1]; ++v)
                 for (int e = photo_ptr[v]; e < photo_ptr[v + 1]; ++e) lph[e] = (unsigned char)(v - pgrp_ptr[g]);
         HIPC(p->edge_lphoto.upload(lph.data(), lph.size()));
+        // k_group's per-group headers (kGHdr*, mcc_internal.h): the ranges, the group-relative photo_ptr
+        // entries and the first round's edge records at a fixed stride
+        std::vector<int> hdr((size_t)mcc::kGHdrInts * std::max(NG, 1), 0);
+        for (int g = 0; g < NG; ++g) {
+            int* h = hdr.data() + (size_t)mcc::kGHdrInts * g;
+            const int p0 = pgrp_ptr[g], np = pgrp_ptr[g + 1] - p0, ge0 = photo_ptr[p0], gne = photo_ptr[p0 + np] - ge0;
+            h[0] = p0; h[1] = np; h[2] = ge0; h[3] = gne;
+            h[4] = gpair_ptr[g]; h[5] = gpair_ptr[g + 1] - gpair_ptr[g];
+            h[6] = gcon_ptr[g]; h[7] = gcon_ptr[g + 1] - gcon_ptr[g];
+            for (int q = 0; q <= mcc::kPhotoGroup; ++q) h[mcc::kGHdrPhoto + q] = photo_ptr[p0 + std::min(q, np)] - ge0;
+            for (int le = 0; le < std::min(gne, mcc::kGroupRound); ++le) {
+                const int4 f = info[ge0 + le];
+                int* hi = h + mcc::kGHdrInfo + 4 * le;
+                hi[0] = f.x; hi[1] = f.y; hi[2] = f.z; hi[3] = f.w;
+                h[mcc::kGHdrGb + le] = gblock[ge0 + le];
+                h[mcc::kGHdrEq + le] = lph[ge0 + le];
+            }
+        }
+        HIPC(p->ghdr.upload(hdr.data(), hdr.size()));
+        // the cameras' intrinsics rows as k_group keeps them in LDS: fx fy cx cy skew xi k[12] matTilt[9] pad,
+        // each the float's exact value in FP64
+        std::vector<double> kin((size_t)mcc::kGIntr * C, 0.0);
+        for (int c = 0; c < C; ++c) {
+            double* kt = kin.data() + (size_t)mcc::kGIntr * c;
+            const float* Kc = d->K + 9 * c;
+            kt[0] = Kc[0]; kt[1] = Kc[4]; kt[2] = Kc[2]; kt[3] = Kc[5]; kt[4] = Kc[1];
+            kt[5] = d->model == MCC_MODEL_OMNI ? (double)xi[c] : 0.0;
+            for (int q = 0; q < 12; ++q) kt[6 + q] = q < d->nd ? (double)d->D[d->nd * c + q] : 0.0;
+            if (p->prism == 2) tilt_matrix(d->D[14 * c + 12], d->D[14 * c + 13], kt + 18);
+        }
+        HIPC(p->kintr.upload(kin.data(), kin.size()));
     }
     if (!p->fused && !p->use_group) {
         // k_prep4's groups: consecutive photos, <= kPrepPhotos of them and kPrepEdges edges (or one photo)
@@ -1315,6 +1349,7 @@ void mcc_destroy(mcc_problem* p) {
     p->photo_ptr.release(); p->photo_corner.release(); p->edge_gblock.release(); p->block_items.release(); p->counter.release(); p->cnt_blk.release();
     p->edge_photo.release(); p->edge_info.release(); p->items.release(); p->gpairs.release();
     p->prep_ptr.release(); p->prep_edge.release();
+    p->ghdr.release(); p->kintr.release();
     p->pgrp_ptr.release(); p->pgrp_edge.release(); p->edge_lphoto.release(); p->gpair_ptr.release(); p->gcon_ptr.release(); p->gcon.release();
     p->state.release();
     if (p->h_state) (void)hipHostFree(p->h_state);

@@ -4,8 +4,12 @@
 // photos and kGroupRound edges, or one photo with more edges), doing in ONE launch what k_prep,
 // k_edge and k_photo do in three (src/mymulticalib.cpp:468-614, 668-818; src/multicalib.cpp:593-824;
 // src/doubleSide.cpp:288-581):
-//   phase 0  loads of the group (one round trip: edge records, Schur pair lists, the previous step's
-//            Y', z', dg, the cameras, the first round's corners); the pending photo update
+//   phase 0  loads of the group in three dependent stages: a scalar batch (the state, the group's
+//            host-built header: LinArgs::ghdr), one vector batch into registers (edge records, Schur
+//            pair lists, the previous step's Y', z', dg, the cameras and their prebuilt intrinsics
+//            rows: LinArgs::kintr) and the first round's corners, whose addresses come from the header
+//            record and whose registers reach LDS only after the photo work below (edges past the
+//            header's 16 and lists longer than one pass per thread: cold loops); the pending photo update
 //            x = fl32(x + fl32(alpha (z' - sum_e Y'_e^T dg))) (k_prep's, group-cooperative), the
 //            cameras' Rodrigues tables (one lane per camera), the photos' Rodrigues (one lane per
 //            photo);
@@ -739,13 +743,15 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
     constexpr int NT = kGroupRound * L, EPW = 64 / L;   // threads; edges per wave
     State* st = a.state;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // ---- round trip 1: the state and the group's ranges (the stop test after the loads are issued)
+    const int wv = __builtin_amdgcn_readfirstlane(wave);   // (uniform: a whole wave's loads are skipped by a scalar branch)
+    // ---- scalar batch: the state and the group's header (the stop test after the loads are issued)
+    const int* __restrict__ hdr = a.ghdr + (size_t)kGHdrInts * grp;
     const int done = st->done, pending = st->pending;
     const double alpha_prev = st->alpha;   // step factor of the pending update
-    const int p0 = a.pgrp_ptr[grp], np = a.pgrp_ptr[grp + 1] - p0;
-    const int ge0 = a.pgrp_edge[grp], gne = a.pgrp_edge[grp + 1] - ge0;   // the group's edges are contiguous
-    const int q0 = a.gpair_ptr[grp], nq = a.gpair_ptr[grp + 1] - q0;
-    const int c0 = a.gcon_ptr[grp], nc = a.gcon_ptr[grp + 1] - c0;
+    const int p0 = hdr[kGHdrRange], np = hdr[kGHdrRange + 1];
+    const int ge0 = hdr[kGHdrRange + 2], gne = hdr[kGHdrRange + 3];   // the group's edges are contiguous
+    const int q0 = hdr[kGHdrRange + 4], nq = hdr[kGHdrRange + 5];
+    const int c0 = hdr[kGHdrRange + 6], nc = hdr[kGHdrRange + 7];
     if (done) return false;
     long long* stp = a.stamps ? a.stamps + kStampStride * (size_t)grp : nullptr;   // MCC_DIAG: slots 0..11
     SSTAMP(stp, 0, 0);
@@ -778,12 +784,10 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
     static_assert(EPW * sizeof(GroupChain) <= 5 * kGChunk * EPW * sizeof(float), "k_group chain union");
 
     const int g = lane % EPW, sub = lane / EPW;   // edge slot of the wave, lane within the edge
-    // corners of an edge -> this wave's staging (every load of the chunk issued before the first store)
-    auto stage = [&](int eoff, int cc0, int cn) {
-        constexpr int PER = kGChunk / L;
-        float v[PER][5];
-        int sb = sub;
-        asm volatile("" : "+v"(sb));
+    // corners of an edge -> registers (lanes past the edge's corners read its first one), then -> this
+    // wave's staging (every load of the chunk issued before the first store)
+    constexpr int PER = kGChunk / L;
+    auto stage_load = [&](float (&v)[PER][5], int sb, int eoff, int cc0, int cn) {
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const int i = sb + L * u;
@@ -794,6 +798,8 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
             v[u][3] = a.img_u[c];
             v[u][4] = a.img_v[c];
         }
+    };
+    auto stage_store = [&](const float (&v)[PER][5], int sb, int cn) {
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const int i = sb + L * u;
@@ -803,83 +809,134 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
             }
         }
     };
+    auto stage = [&](int eoff, int cc0, int cn) {
+        float v[PER][5];
+        int sb = sub;
+        asm volatile("" : "+v"(sb));
+        stage_load(v, sb, eoff, cc0, cn);
+        stage_store(v, sb, cn);
+    };
 
     // the cameras' (and the double-side transform's) Rodrigues tables are formed by threads outside
     // the photo tasks' wave while those update the photos (k_linearize's wave-1 code)
     constexpr int CAM0 = NT / 2, DST = CAM0 + 63;
     double om2[3] = {0.0, 0.0, 0.0}, T2[3] = {0.0, 0.0, 0.0};
-    // ---- phase 0: every load of the group in one round trip
-    {
-        // the first round's corners (issued first: the longest stream)
-        {
-            const int le = wave * EPW + g;
-            const int4 info = le < gne ? a.edge_info[ge0 + le] : make_int4(0, 0, 0, 0);
-            if (le < gne) stage(info.z, 0, min(info.w, kGChunk));
-        }
-        // edge records, the group's pair lists
-        for (int t = tid; t < gne; t += NT) {
-            sInfo[t] = a.edge_info[ge0 + t];
-            sgb[t] = a.gblock[ge0 + t];
-            seq[t] = a.edge_lphoto[ge0 + t];
-        }
-        if (tid <= np) sph0[tid] = a.photo_ptr[p0 + tid] - ge0;
-        for (int t = tid; t < nq; t += NT) spq[t] = a.gpairs[q0 + t];
-        for (int t = tid; t < nc; t += NT) scn[t] = a.gcon[c0 + t];
-        for (int t = tid; t < m; t += NT) sdg[t] = a.dg[t];
-        if (tid >= CAM0 && tid < CAM0 + C) {   // camera tables: loads here, Rodrigues after the partials
-            const int c = tid - CAM0;
-            if (MODEL == MCC_MODEL_DOUBLESIDE) {
+    // ---- phase 0, vector batch: every load whose address the scalar batch gives, issued into registers
+    // before the first wait.  Lanes without a task read element 0 of the same array (selects, no
+    // exec-masked loads); waves without one skip the load by a scalar branch.
+    // (1) this lane's first-round edge record from the header (the corners' addresses need it: first)
+    const int le0 = wave * EPW + g;   // < kGroupRound; the header's records past gne are zeros
+    const int4 info0 = *reinterpret_cast<const int4*>(hdr + kGHdrInfo + 4 * le0);
+    // (2) the first round's edge records and the photos' edge ranges (wave 0 -> LDS)
+    int4 rInfo = make_int4(0, 0, 0, 0);
+    int rGb = 0, rEq = 0, rPh = 0;
+    if (wv == 0) {
+        const int t = lane < kGroupRound ? lane : 0;
+        rInfo = *reinterpret_cast<const int4*>(hdr + kGHdrInfo + 4 * t);
+        rGb = hdr[kGHdrGb + t];
+        rEq = hdr[kGHdrEq + t];
+        rPh = hdr[kGHdrPhoto + (lane <= kPhotoGroup ? lane : 0)];
+    }
+    // (3) the pair and contribution lists, dg, the cameras' intrinsics rows: the first pass of each
+    int4 rPq = make_int4(0, 0, 0, 0);
+    unsigned rCn = 0;
+    double rDg = 0.0, rKt = 0.0;
+    if (wv * 64 < nq) rPq = a.gpairs[q0 + (tid < nq ? tid : 0)];
+    if (wv * 64 < nc) rCn = a.gcon[c0 + (tid < nc ? tid : 0)];
+    if (wv * 64 < m) rDg = a.dg[tid < m ? tid : 0];
+    if (wv * 64 < kGIntr * C) rKt = a.kintr[tid < kGIntr * C ? tid : 0];
+    // (4) the cameras' poses (lane c of the camera wave) and the double-side transform (its lane 63)
+    float rCam[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    double rDs[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (wv == CAM0 / 64) {
+        const int c = lane < C ? lane : 0;
+        const float* src = MODEL == MCC_MODEL_DOUBLESIDE ? a.cam_rt + 6 * c : a.x + 6 * (c > 0 ? c - 1 : 0);
+        if (BACK && MODEL == MCC_MODEL_DOUBLESIDE) src = tid == DST ? a.x : src;   // DoubleSide's global block
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { om2[k] = a.cam_rt[6 * c + k]; T2[k] = a.cam_rt[6 * c + 3 + k]; }
-            } else if (c == 0) {
+        for (int k = 0; k < 6; ++k) rCam[k] = src[k];
+        if (BACK && MODEL != MCC_MODEL_DOUBLESIDE) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { om2[k] = 0.0; T2[k] = 0.0; }   // src/mymulticalib.cpp:721-725
-            } else {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { om2[k] = a.x[6 * (c - 1) + k]; T2[k] = a.x[6 * (c - 1) + 3 + k]; }
-            }
-            double* kt = ktab + kGIntr * c;
-            const float* Kc = a.K + 9 * c;
-            kt[0] = Kc[0]; kt[1] = Kc[4]; kt[2] = Kc[2]; kt[3] = Kc[5]; kt[4] = Kc[1];
-            kt[5] = MODEL == MCC_MODEL_OMNI ? (double)a.xi[c] : 0.0;
-            const int nd = a.nd;
-#pragma unroll
-            for (int q = 0; q < 12; ++q) kt[6 + q] = q < nd ? (double)a.D[nd * c + q] : 0.0;
-            if (PRISM == 2)
-#pragma unroll
-                for (int q = 0; q < 9; ++q) kt[18 + q] = a.tilt[9 * c + q];
-        } else if (BACK && tid == DST) {   // the double-side transform (BACK edges; DoubleSide's global block)
-            if (MODEL == MCC_MODEL_DOUBLESIDE) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { om2[k] = a.x[k]; T2[k] = a.x[3 + k]; }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { om2[k] = a.ds_rt[k]; T2[k] = a.ds_rt[3 + k]; }
-            }
+            for (int k = 0; k < 6; ++k) rDs[k] = a.ds_rt[k];
         }
     }
-    // the pending update's operands: thread (le, k) < 6 gne forms sum_i Y'_e[i][k] dg_g(e)[i]
-    // (k_prep's order; its first task's Y' column and global block loaded in this round trip);
+    // (5) the pending update's operands: thread (le, k) < 6 gne forms sum_i Y'_e[i][k] dg_g(e)[i]
+    // (k_prep's order; its first task's Y' column and global block loaded here);
     // thread 192 + 6q + k < 192 + 6 np: photo q's x_k and z'_k
     float xo = 0.f;
     double zk = 0.0;
     const int pq = (tid - 192) / 6, pk = (tid - 192) % 6;
     const bool ptask = tid >= 192 && pq < np;
     double2 pn0 = make_double2(0.0, 0.0);   // the fold without a pending update: the norms k_backsub left
-    if (ptask) {
-        xo = a.x[m + 6 * (size_t)(p0 + pq) + pk];
-        if (pending) zk = a.zp[6 * (size_t)(p0 + pq) + pk];
-        else if (a.fold && pk == 0) pn0 = *reinterpret_cast<const double2*>(a.photo_norm + 2 * (size_t)(p0 + pq));
+    if (wv == 3) {
+        const size_t pi = ptask ? 6 * (size_t)(p0 + pq) + pk : 0;
+        xo = a.x[m + pi];
+        if (pending) zk = a.zp[pi];
+        else if (a.fold) pn0 = *reinterpret_cast<const double2*>(a.photo_norm + (ptask && pk == 0 ? 2 * (size_t)(p0 + pq) : 0));
     }
-    double y0[6];
+    double y0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     int gb0 = -1;
-    if (pending && tid < 6 * gne) {
-        const int le = tid / 6, k = tid % 6;
+    if (pending && wv * 64 < 6 * gne) {
+        const bool act = tid < 6 * gne;
+        const int le = act ? tid / 6 : 0, k = act ? tid % 6 : 0;
         gb0 = a.gblock[ge0 + le];
         const double* Ye = a.Y + 36 * (size_t)(ge0 + le);
 #pragma unroll
         for (int i = 0; i < 6; ++i) y0[i] = Ye[6 * i + k];
     }
+    // (6) the first round's corners, last: they stay in registers past the barrier (the staging is this
+    // wave's own and is not read before the sweep), so their round trip -- the only one that depends on
+    // a load of this batch -- overlaps the pending update and the Rodrigues work.  Every wave issues
+    // them (an edge slot past gne has no corners: its lanes read corner 0).
+    float cv0[PER][5];
+    int sb0 = sub;
+    asm volatile("" : "+v"(sb0));
+    const int cn0 = min(info0.w, kGChunk);
+    __builtin_amdgcn_sched_barrier(0);
+    stage_load(cv0, sb0, info0.z, 0, cn0);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- the batch -> LDS, in issue order (the corners stay outstanding)
+    // (the poses stay float32 words until here: a conversion folded into the load's block would wait there)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) asm volatile("" : "+v"(rCam[k]));
+    if (wv == 0) {
+        if (lane < kGroupRound && lane < gne) {
+            sInfo[lane] = rInfo;
+            sgb[lane] = rGb;
+            seq[lane] = rEq;
+        }
+        if (lane <= np) sph0[lane] = rPh;
+    }
+    if (tid < nq) spq[tid] = rPq;
+    if (tid < nc) scn[tid] = rCn;
+    if (tid < m) sdg[tid] = rDg;
+    if (tid < kGIntr * C) ktab[tid] = rKt;
+    if (tid >= CAM0 && tid < CAM0 + C) {   // camera tables: Rodrigues after the partials
+        const bool fixed0 = MODEL != MCC_MODEL_DOUBLESIDE && tid == CAM0;   // src/mymulticalib.cpp:721-725
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            om2[k] = fixed0 ? 0.0 : (double)rCam[k];
+            T2[k] = fixed0 ? 0.0 : (double)rCam[3 + k];
+        }
+    } else if (BACK && tid == DST) {   // the double-side transform (BACK edges; DoubleSide's global block)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            om2[k] = MODEL == MCC_MODEL_DOUBLESIDE ? (double)rCam[k] : rDs[k];
+            T2[k] = MODEL == MCC_MODEL_DOUBLESIDE ? (double)rCam[3 + k] : rDs[3 + k];
+        }
+    }
+    // ---- cold: what one pass per thread does not cover (edges past the header's round, longer lists)
+#pragma unroll 1
+    for (int t = kGroupRound + tid; t < gne; t += NT) {
+        sInfo[t] = a.edge_info[ge0 + t];
+        sgb[t] = a.gblock[ge0 + t];
+        seq[t] = a.edge_lphoto[ge0 + t];
+    }
+#pragma unroll 1
+    for (int t = NT + tid; t < nq; t += NT) spq[t] = a.gpairs[q0 + t];
+#pragma unroll 1
+    for (int t = NT + tid; t < nc; t += NT) scn[t] = a.gcon[c0 + t];
+#pragma unroll 1
+    for (int t = NT + tid; t < kGIntr * C; t += NT) ktab[t] = a.kintr[t];
     __syncthreads();
     SSTAMP(stp, 1, 0);
     if (pending) {
@@ -970,6 +1027,9 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
     }
     __syncthreads();
     SSTAMP(stp, 2, 0);
+    // the first round's corners (phase 0's last loads) -> this wave's staging; the prologue's last
+    // wave_sync_lds orders these stores ahead of the sweep's reads
+    stage_store(cv0, sb0, cn0);
 
     // ---- phase A: rounds of 16 edges
     for (int rb = 0; rb < gne; rb += kGroupRound) {

@@ -177,13 +177,27 @@ struct LinArgs {
     SchurArgs fsa;            // the reduction (k_schur's arguments: items, slots, partials, packed, solve)
     double* fnorm;            // [4V] per photo ||G||^2, ||x||^2, not-PD flag, pad (the norm chunks' input)
     double* fiv;              // [m^2 + 1] the spare's inverse and its status, +-(iteration + 1) as a double
+    // k_group's phase 0 (built once in mcc_create; the topology and the intrinsics never change)
+    const int* ghdr;          // [n_pgroups][kGHdrInts] per-group header (layout below)
+    const double* kintr;      // [C][kGIntr] the cameras' intrinsics rows, the kernel's LDS layout in FP64
 };
+// k_group's per-group header (ints, fixed stride): the group's ranges, the group-relative photo_ptr
+// entries and the first round's edge records, so that phase 0 chases no index through memory
+constexpr int kGHdrRange = 0;     // p0, np, ge0, gne, q0, nq, c0, nc
+constexpr int kGHdrPhoto = 8;     // [kPhotoGroup + 1] photo_ptr[p0 + q] - ge0 (entries past np repeat gne)
+constexpr int kGHdrInfo = 20;     // int4 [16] edge_info of the first round's edges (16-byte aligned)
+constexpr int kGHdrGb = 84;       // [16] gblock
+constexpr int kGHdrEq = 100;      // [16] edge_lphoto
+constexpr int kGHdrInts = 128;    // stride (512 bytes)
 constexpr long long kFoldEmpty = -1LL;
 
 constexpr int kItemSingle = 256;   // k_schur item flag (in .w, over the slot size): the block's only item
 constexpr int kPhotoGroup = 8;        // photos per k_photo workgroup, at most
 constexpr int kPhotoGroupEdges = 64;  // edges per k_photo workgroup, at most
 constexpr int kGroupRound = 16;       // edges per k_group round (4 waves x 4 edges x 16 lanes); its groups' cap
+static_assert(kGHdrPhoto + kPhotoGroup + 1 <= kGHdrInfo && kGHdrInfo % 4 == 0 && kGHdrInfo + 4 * kGroupRound == kGHdrGb &&
+                  kGHdrGb + kGroupRound == kGHdrEq && kGHdrEq + kGroupRound <= kGHdrInts,
+              "k_group header layout");
 // k_photo's LDS (doubles, then ints): per edge [Hgg upper 21 | pad | U 36 | gg 6] (64), per photo the
 // Hpp / gp sums [28], Hpp's inverse Cholesky factor Li [36] and v [6]; then per edge gblock and
 // photo (ints), the group's pairs (int4) and contributions (unsigned)
