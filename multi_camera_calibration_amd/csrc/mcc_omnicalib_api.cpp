@@ -473,6 +473,7 @@ int mcc_omnidir_calibrate(int n_img, const int* off, const double* obj, const do
     // src/omnidir.cpp:1067-1211: initialise, keep the idx views, encodeParameters(K, om, t, D = 0,
     // xi), the loop, decodeParameters, estimateUncertainties' rms
     if (!K || !xi || !D || !om || !t || !idx || !n_idx || !rms) return oc_fail(MCC_EINVAL, "null argument");
+    if (crit_type < 1 || crit_type > 3) return oc_fail(MCC_EINVAL, "crit_type must be 1, 2 or 3");
     std::vector<double> om0(3 * (size_t)std::max(n_img, 1)), t0(om0.size());
     double K0[9], xi0 = 1;
     int nk = 0;

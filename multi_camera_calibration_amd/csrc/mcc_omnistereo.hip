@@ -72,6 +72,23 @@ __device__ __forceinline__ void os_right_pose(const double* pl, const double* gl
     so3_jac(w2, r2, +1.0, Jl2);
     double th, s, c;
     compose(r1.R, Jr1, T1, r2.R, Jl2, T2, m, th, s, c);
+    if (s < 1e-5 && c > 0) {
+        // cvRodrigues2's s < 1e-5, c > 0 branch: om3 = 0 and d om3 / d R3 is the fixed +-0.5 pattern
+        // of om3 = vee(R3 - R3^T) / 2, so d om3 / d omL = (tr(R3) I - R3^T) / 2 Jr(omL) and
+        // d om3 / d om = (tr(R3) I - R3) / 2 Jl(om); compose()'s closed form at om3 = 0 is the
+        // identity there, O(theta) away
+        const double tr = m.R[0] + m.R[4] + m.R[8];
+        double Pr[9], Pl[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                Pl[i * 3 + j] = 0.5 * ((i == j ? tr : 0.0) - m.R[i * 3 + j]);
+                Pr[i * 3 + j] = 0.5 * ((i == j ? tr : 0.0) - m.R[j * 3 + i]);
+            }
+        mat3_mul(Pr, Jr1, m.A1);
+        mat3_mul(Pl, Jl2, m.A2);
+    }
     oc_pose(m.om, R3, J3);
 #pragma unroll
     for (int k = 0; k < 3; ++k) T3[k] = m.T[k];
