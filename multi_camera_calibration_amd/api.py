@@ -141,29 +141,22 @@ def lib():
         L.mcc_peer_init.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]
         L.mcc_peer_enable.argtypes = [ctypes.c_void_p, ctypes.c_int]
         # include/mcc_omnidir.h
-        L.mcc_omnicalib_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_OmniDesc)]
-        L.mcc_omnicalib_destroy.argtypes = [ctypes.c_void_p]
-        L.mcc_omnicalib_destroy.restype = None
-        L.mcc_omnicalib_nparams.argtypes = [ctypes.c_void_p]
-        L.mcc_omnicalib_jacobian.argtypes = [ctypes.c_void_p, _f64p, ctypes.c_int, _f64p, _f64p]
-        L.mcc_omnicalib_optimize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, _f64p,
-                                             _i32p, _f64p]
-        L.mcc_omnicalib_rms.argtypes = [ctypes.c_void_p, _f64p, _f64p]
-        L.mcc_omnicalib_time_steps.argtypes = [ctypes.c_void_p, _f64p, ctypes.c_int, _f64p]
+        for pre, desc in (("omnicalib", _OmniDesc), ("omnistereo", _OmniStereoDesc)):
+            f = {k: getattr(L, f"mcc_{pre}_{k}")
+                 for k in ("create", "destroy", "nparams", "jacobian", "optimize", "rms", "time_steps")}
+            f["create"].argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(desc)]
+            f["destroy"].argtypes = [ctypes.c_void_p]
+            f["destroy"].restype = None
+            f["nparams"].argtypes = [ctypes.c_void_p]
+            f["jacobian"].argtypes = [ctypes.c_void_p, _f64p, ctypes.c_int, _f64p, _f64p]
+            f["optimize"].argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, _f64p, _i32p, _f64p]
+            f["rms"].argtypes = [ctypes.c_void_p, _f64p, _f64p]
+            f["time_steps"].argtypes = [ctypes.c_void_p, _f64p, ctypes.c_int, _f64p]
         L.mcc_omnidir_initialize.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _f64p,
                                              _f64p, _f64p, _f64p, _i32p, _i32p]
         L.mcc_omnidir_calibrate.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                             _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p, _f64p, _i32p]
-        L.mcc_omnistereo_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_OmniStereoDesc)]
-        L.mcc_omnistereo_destroy.argtypes = [ctypes.c_void_p]
-        L.mcc_omnistereo_destroy.restype = None
-        L.mcc_omnistereo_nparams.argtypes = [ctypes.c_void_p]
-        L.mcc_omnistereo_jacobian.argtypes = [ctypes.c_void_p, _f64p, ctypes.c_int, _f64p, _f64p]
-        L.mcc_omnistereo_optimize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, _f64p,
-                                              _i32p, _f64p]
-        L.mcc_omnistereo_rms.argtypes = [ctypes.c_void_p, _f64p, _f64p]
-        L.mcc_omnistereo_time_steps.argtypes = [ctypes.c_void_p, _f64p, ctypes.c_int, _f64p]
         L.mcc_omnidir_stereo_encode_init.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, ctypes.c_int, _i32p, _f64p,
                                                      _f64p, _f64p, ctypes.c_double, _f64p, _f64p, ctypes.c_double,
                                                      _f64p, _f64p, _i32p, _i32p]
@@ -501,9 +494,55 @@ def _views(off, obj, img):
     return off, obj, img
 
 
-class OmniCalibrator:
+class _OmniLoop:
+    """What OmniCalibrator and OmniStereoCalibrator share: the handle's life and the calls into the
+    device loop, mcc_<_prefix>_* of include/mcc_omnidir.h."""
+    _prefix = None
+
+    def _call(self, name, *args):
+        fn = f"mcc_{self._prefix}_{name}"
+        _check(getattr(lib(), fn)(self.h, *args), fn)
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(lib(), f"mcc_{self._prefix}_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def compute_jacobian(self, params, it=0):
+        p = np.ascontiguousarray(params, np.float64)
+        jte, G = np.zeros(self.P), np.zeros(self.P)
+        self._call("jacobian", _ptr(p, _f64p), it, _ptr(jte, _f64p), _ptr(G, _f64p))
+        return jte, G
+
+    def optimize(self, params, crit_type=MCC_CRIT_COUNT_EPS, max_count=200, eps=1e-4):
+        p = np.array(params, np.float64, copy=True)
+        it, ch = ctypes.c_int(0), ctypes.c_double(0)
+        self._call("optimize", crit_type, max_count, eps, _ptr(p, _f64p), ctypes.byref(it), ctypes.byref(ch))
+        return p, it.value, ch.value
+
+    def rms(self, params):
+        p = np.ascontiguousarray(params, np.float64)
+        r = ctypes.c_double(0)
+        self._call("rms", _ptr(p, _f64p), ctypes.byref(r))
+        return r.value
+
+    def time_steps(self, params, n_steps):
+        p = np.ascontiguousarray(params, np.float64)
+        ms = ctypes.c_double(0)
+        self._call("time_steps", _ptr(p, _f64p), n_steps, ctypes.byref(ms))
+        return ms.value
+
+
+class OmniCalibrator(_OmniLoop):
     """The device-resident state of cv::omnidir::calibrate's loop for one camera's views
     (CV_64F pattern / image points, parameters in encodeParameters layout, P = 6n + 10)."""
+    _prefix = "omnicalib"
 
     def __init__(self, off, obj, img, flags: int = 0, device: int = 0):
         self.off, self.obj, self.img = _views(off, obj, img)
@@ -518,45 +557,13 @@ class OmniCalibrator:
         self.h = h
         self.P = lib().mcc_omnicalib_nparams(h)
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().mcc_omnicalib_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def compute_jacobian(self, params, it=0):
         """(JTE before the flag reduction, G of loop iteration `it`) at params (computeJacobian)."""
-        p = np.ascontiguousarray(params, np.float64)
-        jte, G = np.zeros(self.P), np.zeros(self.P)
-        _check(lib().mcc_omnicalib_jacobian(self.h, _ptr(p, _f64p), it, _ptr(jte, _f64p), _ptr(G, _f64p)),
-               "mcc_omnicalib_jacobian")
-        return jte, G
+        return super().compute_jacobian(params, it)
 
     def optimize(self, params, crit_type=MCC_CRIT_COUNT_EPS, max_count=200, eps=1e-4):
         """calibrate's loop: (params, iterations, last change)."""
-        p = np.array(params, np.float64, copy=True)
-        it, ch = ctypes.c_int(0), ctypes.c_double(0)
-        _check(lib().mcc_omnicalib_optimize(self.h, crit_type, max_count, eps, _ptr(p, _f64p), ctypes.byref(it),
-                                            ctypes.byref(ch)), "mcc_omnicalib_optimize")
-        return p, it.value, ch.value
-
-    def rms(self, params):
-        p = np.ascontiguousarray(params, np.float64)
-        r = ctypes.c_double(0)
-        _check(lib().mcc_omnicalib_rms(self.h, _ptr(p, _f64p), ctypes.byref(r)), "mcc_omnicalib_rms")
-        return r.value
-
-    def time_steps(self, params, n_steps):
-        p = np.ascontiguousarray(params, np.float64)
-        ms = ctypes.c_double(0)
-        _check(lib().mcc_omnicalib_time_steps(self.h, _ptr(p, _f64p), n_steps, ctypes.byref(ms)),
-               "mcc_omnicalib_time_steps")
-        return ms.value
+        return super().optimize(params, crit_type, max_count, eps)
 
 
 def omnidir_initialize(off, obj, img, image_size):
@@ -603,10 +610,11 @@ def _stereo_views(off, obj, img1, img2):
     return off, obj, img1, img2
 
 
-class OmniStereoCalibrator:
+class OmniStereoCalibrator(_OmniLoop):
     """The device-resident state of cv::omnidir::stereoCalibrate's loop for the views both cameras
     see (CV_64F points, the same corner count in every view; parameters in encodeParametersStereo
     layout, P = 6(n + 1) + 20)."""
+    _prefix = "omnistereo"
 
     def __init__(self, off, obj, img1, img2, flags: int = 0, device: int = 0):
         self.off, self.obj, self.img1, self.img2 = _stereo_views(off, obj, img1, img2)
@@ -622,45 +630,13 @@ class OmniStereoCalibrator:
         self.h = h
         self.P = lib().mcc_omnistereo_nparams(h)
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().mcc_omnistereo_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def compute_jacobian(self, params, it=0):
         """(JTE before the flag reduction, G of loop iteration `it`) at params (computeJacobianStereo)."""
-        p = np.ascontiguousarray(params, np.float64)
-        jte, G = np.zeros(self.P), np.zeros(self.P)
-        _check(lib().mcc_omnistereo_jacobian(self.h, _ptr(p, _f64p), it, _ptr(jte, _f64p), _ptr(G, _f64p)),
-               "mcc_omnistereo_jacobian")
-        return jte, G
+        return super().compute_jacobian(params, it)
 
     def optimize(self, params, crit_type=MCC_CRIT_COUNT_EPS, max_count=200, eps=1e-4):
         """stereoCalibrate's loop: (params, iterations, last change)."""
-        p = np.array(params, np.float64, copy=True)
-        it, ch = ctypes.c_int(0), ctypes.c_double(0)
-        _check(lib().mcc_omnistereo_optimize(self.h, crit_type, max_count, eps, _ptr(p, _f64p), ctypes.byref(it),
-                                             ctypes.byref(ch)), "mcc_omnistereo_optimize")
-        return p, it.value, ch.value
-
-    def rms(self, params):
-        p = np.ascontiguousarray(params, np.float64)
-        r = ctypes.c_double(0)
-        _check(lib().mcc_omnistereo_rms(self.h, _ptr(p, _f64p), ctypes.byref(r)), "mcc_omnistereo_rms")
-        return r.value
-
-    def time_steps(self, params, n_steps):
-        p = np.ascontiguousarray(params, np.float64)
-        ms = ctypes.c_double(0)
-        _check(lib().mcc_omnistereo_time_steps(self.h, _ptr(p, _f64p), n_steps, ctypes.byref(ms)),
-               "mcc_omnistereo_time_steps")
-        return ms.value
+        return super().optimize(params, crit_type, max_count, eps)
 
 
 def omnidir_stereo_encode_init(idx1, om1, t1, idx2, om2, t2, K1, xi1, D1, K2, xi2, D2):

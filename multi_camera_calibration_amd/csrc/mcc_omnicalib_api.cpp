@@ -18,84 +18,24 @@
 #include "mcc_omnicalib_host.hpp"
 #include "mcc_omnicalib_internal.h"
 
-using mcc::OcState;
+struct mcc_omnicalib : OcHandle {
+    static constexpr int kG = 10;
+    static constexpr const char* kName = "omnidir calibrate";
+    static constexpr const char* kStepName = "k_oc_step";
+    int max_np = 1;
+    DBuf<double> ox, oy, oz, iu, iv;
+    DBuf<int> view_off;
 
-struct mcc_omnicalib {
-    int n = 0, P = 0, flags = 0, device = 0, max_np = 1, group_size = 1, n_groups = 1;
-    long long corners = 0;
-    std::vector<int> off;
-    hipStream_t stream = nullptr;
-    DBuf<double> ox, oy, oz, iu, iv, x, mask, Yv, zb, zu, yc, jte, G, contrib, gsum, view_sq;
-    DBuf<int> view_off, cnt;
-    DBuf<OcState> st;
-    OcState* h_st = nullptr;
-    static constexpr int kGraphSteps = 8;
-    hipGraphExec_t gexec[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-
-    mcc::OcArgs args() const {
-        return mcc::OcArgs{st.p, view_off.p, ox.p, oy.p, oz.p, iu.p, iv.p, x.p, mask.p, Yv.p, zb.p, zu.p, yc.p,
-                           jte.p, G.p, contrib.p, gsum.p, cnt.p, n, group_size, n_groups, max_np};
+    hipError_t launch_step() const {
+        return mcc_launch_oc_step(mcc::OcArgs{loop(), view_off.p, ox.p, oy.p, oz.p, iu.p, iv.p, max_np}, stream);
     }
+    hipError_t launch_err() const {
+        return mcc_launch_oc_err(mcc::OcErrArgs{view_off.p, ox.p, oy.p, oz.p, iu.p, iv.p, x.p, view_sq.p, n}, stream);
+    }
+    double rms_points() const { return (double)corners; }
 };
 
 namespace {
-
-int oc_set_state(mcc_omnicalib* h, int iter, int crit, int max_count, double eps) {
-    OCCHK(hipStreamSynchronize(h->stream));
-    OcState s{};
-    s.iter = iter;
-    s.crit_type = crit;
-    s.max_count = max_count;
-    s.eps = eps;
-    s.change = 1.0;
-    *h->h_st = s;
-    OCCHK(hipMemcpyAsync(h->st.p, h->h_st, sizeof(OcState), hipMemcpyHostToDevice, h->stream));
-    OCCHK(hipStreamSynchronize(h->stream));
-    return MCC_OK;
-}
-
-int oc_read_state(mcc_omnicalib* h) {
-    OCCHK(hipMemcpyAsync(h->h_st, h->st.p, sizeof(OcState), hipMemcpyDeviceToHost, h->stream));
-    OCCHK(hipStreamSynchronize(h->stream));
-    if (h->h_st->error & 1) return oc_fail(MCC_ENOTPD, "omnidir calibrate: a view's 6x6 pose block J^T J is not positive definite");
-    if (h->h_st->error & 2) return oc_fail(MCC_ENOTPD, "omnidir calibrate: the reduced intrinsic system is not positive definite");
-    return MCC_OK;
-}
-
-int oc_upload_params(mcc_omnicalib* h, const double* params) {
-    OCCHK(hipMemcpyAsync(h->x.p, params, sizeof(double) * h->P, hipMemcpyHostToDevice, h->stream));
-    return MCC_OK;
-}
-
-int oc_build_graphs(mcc_omnicalib* h) {
-    if (h->gexec[0]) return MCC_OK;
-    const int counts[2] = {1, mcc_omnicalib::kGraphSteps};
-    const mcc::OcArgs a = h->args();
-    for (int g = 0; g < 2; ++g) {
-        hipGraph_t graph;
-        OCCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        hipError_t le = hipSuccess;
-        for (int s = 0; s < counts[g] && le == hipSuccess; ++s) le = mcc_launch_oc_step(a, h->stream);
-        hipError_t ee = hipStreamEndCapture(h->stream, &graph);
-        if (le != hipSuccess) return oc_fail(MCC_EHIP, std::string("k_oc_step launch: ") + hipGetErrorString(le));
-        if (ee != hipSuccess) return oc_fail(MCC_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ee));
-        OCCHK(hipGraphInstantiate(&h->gexec[g], graph, nullptr, nullptr, 0));
-        OCCHK(hipGraphDestroy(graph));
-    }
-    return MCC_OK;
-}
-
-int oc_launch_steps(mcc_omnicalib* h, int n) {
-    int rc = oc_build_graphs(h);
-    if (rc) return rc;
-    while (n >= mcc_omnicalib::kGraphSteps) {
-        OCCHK(hipGraphLaunch(h->gexec[1], h->stream));
-        n -= mcc_omnicalib::kGraphSteps;
-    }
-    while (n-- > 0) OCCHK(hipGraphLaunch(h->gexec[0], h->stream));
-    return MCC_OK;
-}
 
 // ---------------------------------------------------------------- initializeCalibration (host)
 
@@ -146,15 +86,8 @@ void svd_jacobi(std::vector<double>& A, int m, int k, double* V, double* sv) {
 // omnidir::projectPoints without distortion (D = 0) for xi and K = [g 0 u0; 0 g v0] (init only)
 void project_nodist(int np, const double* obj, const double* om, const double* t, double g, double u0, double v0,
                     double xi, double* out) {
-    const double th = std::sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (th >= 2.220446049250313e-16) {
-        const double c = std::cos(th), s = std::sin(th), c1 = 1 - c;
-        const double x = om[0] / th, y = om[1] / th, z = om[2] / th;
-        const double rrt[9] = {x * x, x * y, x * z, x * y, y * y, y * z, x * z, y * z, z * z};
-        const double rx[9] = {0, -z, y, z, 0, -x, -y, x, 0};
-        for (int k = 0; k < 9; ++k) R[k] = c * ((k % 4 == 0) ? 1.0 : 0.0) + c1 * rrt[k] + s * rx[k];
-    }
+    double R[9];
+    rodrigues_host(om, R);
     for (int i = 0; i < np; ++i) {
         const double* X = obj + 3 * (size_t)i;
         double Xc[3];
@@ -200,160 +133,45 @@ int mcc_omnicalib_create(mcc_omnicalib** out, const mcc_omnicalib_desc* d) {
     h->flags = d->flags;
     h->device = d->device;
     h->max_np = max_np;
-    h->off.assign(d->view_off, d->view_off + n + 1);
-    h->corners = h->off[n];
-    h->group_size = std::max(1, (int)std::ceil(std::sqrt((double)n)));
-    h->n_groups = (n + h->group_size - 1) / h->group_size;
-    auto bail = [&](int rc) {
+    h->corners = d->view_off[n];
+    const int rc = [&] {
+        OCCHK(hipSetDevice(d->device));
+        OCCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        const size_t C = (size_t)h->corners;
+        OCCHK(oc_upload_soa(d->obj, 3, C, {&h->ox, &h->oy, &h->oz}));
+        OCCHK(oc_upload_soa(d->img, 2, C, {&h->iu, &h->iv}));
+        OCCHK(h->view_off.upload(d->view_off, n + 1));
+        double m[10];
+        intrinsic_mask(d->flags, m);
+        OCCHK(h->mask.upload(m, 10));
+        OCCHK(mcc_oc_set_attrs(max_np));
+        return oc_alloc_loop(h);
+    }();
+    if (rc) {
         mcc_omnicalib_destroy(h);
         return rc;
-    };
-#define OCCHK_H(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) return bail(oc_fail(MCC_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-    } while (0)
-    OCCHK_H(hipSetDevice(d->device));
-    OCCHK_H(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    const size_t C = (size_t)h->corners;
-    std::vector<double> soa[5];
-    for (auto& s : soa) s.resize(C);
-    for (size_t c = 0; c < C; ++c) {
-        soa[0][c] = d->obj[3 * c];
-        soa[1][c] = d->obj[3 * c + 1];
-        soa[2][c] = d->obj[3 * c + 2];
-        soa[3][c] = d->img[2 * c];
-        soa[4][c] = d->img[2 * c + 1];
     }
-    OCCHK_H(h->ox.upload(soa[0].data(), C));
-    OCCHK_H(h->oy.upload(soa[1].data(), C));
-    OCCHK_H(h->oz.upload(soa[2].data(), C));
-    OCCHK_H(h->iu.upload(soa[3].data(), C));
-    OCCHK_H(h->iv.upload(soa[4].data(), C));
-    OCCHK_H(h->view_off.upload(h->off.data(), n + 1));
-    double m[10];
-    intrinsic_mask(d->flags, m);
-    OCCHK_H(h->mask.upload(m, 10));
-    OCCHK_H(h->x.alloc(h->P));
-    OCCHK_H(h->Yv.alloc(60 * (size_t)n));
-    OCCHK_H(h->zb.alloc(6 * (size_t)n));
-    OCCHK_H(h->zu.alloc(6 * (size_t)n));
-    OCCHK_H(h->yc.alloc(10));
-    OCCHK_H(h->jte.alloc(h->P));
-    OCCHK_H(h->G.alloc(h->P));
-    OCCHK_H(h->contrib.alloc((size_t)n * mcc::kOcLc));
-    OCCHK_H(h->gsum.alloc((size_t)h->n_groups * mcc::kOcLc));
-    OCCHK_H(h->view_sq.alloc(n));
-    OCCHK_H(h->cnt.alloc(h->n_groups + 1));
-    OCCHK_H(hipMemset(h->cnt.p, 0, sizeof(int) * (h->n_groups + 1)));
-    OCCHK_H(hipMemset(h->G.p, 0, sizeof(double) * h->P));
-    OCCHK_H(hipMemset(h->jte.p, 0, sizeof(double) * h->P));
-    OCCHK_H(h->st.alloc(1));
-    OCCHK_H(hipHostMalloc((void**)&h->h_st, sizeof(OcState), hipHostMallocDefault));
-    OCCHK_H(mcc_oc_set_attrs(max_np));
-    OCCHK_H(hipEventCreate(&h->ev[0]));
-    OCCHK_H(hipEventCreate(&h->ev[1]));
-#undef OCCHK_H
     *out = h;
     return MCC_OK;
 }
 
-void mcc_omnicalib_destroy(mcc_omnicalib* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto& g : h->gexec)
-        if (g) (void)hipGraphExecDestroy(g);
-    for (auto& e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (DBuf<double>* b : {&h->ox, &h->oy, &h->oz, &h->iu, &h->iv, &h->x, &h->mask, &h->Yv, &h->zb, &h->zu, &h->yc,
-                            &h->jte, &h->G, &h->contrib, &h->gsum, &h->view_sq})
-        b->release();
-    h->view_off.release();
-    h->cnt.release();
-    h->st.release();
-    if (h->h_st) (void)hipHostFree(h->h_st);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void mcc_omnicalib_destroy(mcc_omnicalib* h) { oc_destroy(h); }
 
 int mcc_omnicalib_nparams(const mcc_omnicalib* h) { return h ? h->P : MCC_EINVAL; }
 
 int mcc_omnicalib_jacobian(mcc_omnicalib* h, const double* params, int iter, double* jte, double* G) {
-    if (!h || !params || iter < 0) return oc_fail(MCC_EINVAL, "bad argument");
-    OCCHK(hipSetDevice(h->device));
-    int rc = oc_set_state(h, iter, MCC_CRIT_COUNT, iter + 1, 0.0);
-    if (rc) return rc;
-    if ((rc = oc_upload_params(h, params))) return rc;
-    // step 1 linearises and solves iteration `iter` (the intrinsic part of G), step 2 applies the
-    // pending pose update (the pose part of G) and stops (iter + 1 >= max_count)
-    // (step 2 linearises again at the updated point: JTE is read between the two)
-    const mcc::OcArgs a = h->args();
-    OCCHK(mcc_launch_oc_step(a, h->stream));
-    if ((rc = oc_read_state(h))) return rc;
-    if (jte) OCCHK(hipMemcpy(jte, h->jte.p, sizeof(double) * h->P, hipMemcpyDeviceToHost));
-    OCCHK(mcc_launch_oc_step(a, h->stream));
-    if ((rc = oc_read_state(h))) return rc;
-    if (G) OCCHK(hipMemcpy(G, h->G.p, sizeof(double) * h->P, hipMemcpyDeviceToHost));
-    return MCC_OK;
+    return oc_jacobian(h, params, iter, jte, G);
 }
 
 int mcc_omnicalib_optimize(mcc_omnicalib* h, int crit_type, int max_count, double eps, double* params_inout,
                            int* iters, double* last_change) {
-    if (!h || !params_inout) return oc_fail(MCC_EINVAL, "null argument");
-    if (crit_type < 1 || crit_type > 3) return oc_fail(MCC_EINVAL, "crit_type must be 1, 2 or 3");
-    OCCHK(hipSetDevice(h->device));
-    int rc = oc_set_state(h, 0, crit_type, max_count, eps);
-    if (rc) return rc;
-    if ((rc = oc_upload_params(h, params_inout))) return rc;
-    const long long cap = crit_type == MCC_CRIT_EPS ? 1000000LL : (long long)max_count + 1;
-    long long launched = 0;
-    while (true) {
-        if ((rc = oc_launch_steps(h, mcc_omnicalib::kGraphSteps))) return rc;
-        launched += mcc_omnicalib::kGraphSteps;
-        if ((rc = oc_read_state(h))) return rc;
-        if (h->h_st->done) break;
-        if (launched > cap + mcc_omnicalib::kGraphSteps) return oc_fail(MCC_EINVAL, "omnidir calibrate did not terminate");
-    }
-    if (iters) *iters = h->h_st->iter;
-    if (last_change) *last_change = h->h_st->change;
-    OCCHK(hipMemcpy(params_inout, h->x.p, sizeof(double) * h->P, hipMemcpyDeviceToHost));
-    return MCC_OK;
+    return oc_optimize(h, crit_type, max_count, eps, params_inout, iters, last_change);
 }
 
-int mcc_omnicalib_rms(mcc_omnicalib* h, const double* params, double* rms) {
-    if (!h || !params || !rms) return oc_fail(MCC_EINVAL, "null argument");
-    OCCHK(hipSetDevice(h->device));
-    OCCHK(hipStreamSynchronize(h->stream));
-    int rc = oc_upload_params(h, params);
-    if (rc) return rc;
-    const mcc::OcErrArgs a{h->view_off.p, h->ox.p, h->oy.p, h->oz.p, h->iu.p, h->iv.p, h->x.p, h->view_sq.p, h->n};
-    OCCHK(mcc_launch_oc_err(a, h->stream));
-    std::vector<double> sq(h->n);
-    OCCHK(hipMemcpyAsync(sq.data(), h->view_sq.p, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    OCCHK(hipStreamSynchronize(h->stream));
-    double s = 0;
-    for (int v = 0; v < h->n; ++v) s += sq[v];   // view order
-    *rms = std::sqrt(s / (double)h->corners);
-    return MCC_OK;
-}
+int mcc_omnicalib_rms(mcc_omnicalib* h, const double* params, double* rms) { return oc_rms(h, params, rms); }
 
 int mcc_omnicalib_time_steps(mcc_omnicalib* h, const double* params, int n_steps, double* ms_per_step) {
-    if (!h || !params || n_steps < 1 || !ms_per_step) return oc_fail(MCC_EINVAL, "bad argument");
-    OCCHK(hipSetDevice(h->device));
-    int rc = oc_set_state(h, 0, 0, 0, 0.0);
-    if (rc) return rc;
-    if ((rc = oc_upload_params(h, params))) return rc;
-    if ((rc = oc_launch_steps(h, 2))) return rc;   // graph instantiation + first touch
-    OCCHK(hipEventRecord(h->ev[0], h->stream));
-    if ((rc = oc_launch_steps(h, n_steps))) return rc;
-    OCCHK(hipEventRecord(h->ev[1], h->stream));
-    OCCHK(hipEventSynchronize(h->ev[1]));
-    if ((rc = oc_read_state(h))) return rc;
-    float ms = 0.f;
-    OCCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    *ms_per_step = (double)ms / n_steps;
-    return MCC_OK;
+    return oc_time_steps(h, params, n_steps, ms_per_step);
 }
 
 int mcc_omnidir_initialize(int n_img, const int* off, const double* obj, const double* img, int width, int height,

@@ -8,16 +8,24 @@
 
 namespace mcc {
 
-// packed per-view contribution (and group / total sums) of one loop step
-constexpr int kOcS = 0;      // [55] S_v = V_v - W_v^T U_v^-1 W_v, upper triangle of 10 x 10, row-major
-constexpr int kOcRb = 55;    // [10] rc_v - W_v^T U_v^-1 rp_v            (reduced rhs of JTE)
-constexpr int kOcWu = 65;    // [10] W_v^T U_v^-1 1                      (reduced rhs of the ones vector)
-constexpr int kOcJc = 75;    // [10] rc_v = JIn^T E                      (the intrinsic JTE)
-constexpr int kOcAb = 85;    //      1^T U_v^-1 rp_v
-constexpr int kOcAu = 86;    //      1^T U_v^-1 1
-constexpr int kOcNg = 87;    //      |G_pose|^2 of the update applied in phase 0
-constexpr int kOcNx = 88;    //      |x_pose|^2 before it
-constexpr int kOcLc = 89;
+// packed per-view contribution (and group / total sums) of one loop step, for a global block of
+// G parameters (10: one camera's intrinsics; 26: om, T and two cameras' intrinsics)
+template <int G>
+struct OcLayout {
+    static constexpr int S = 0;                   // [G(G+1)/2] S_v = V_v - W_v^T U_v^-1 W_v, upper triangle, row-major
+    static constexpr int Rb = G * (G + 1) / 2;    // [G] rc_v - W_v^T U_v^-1 rp_v   (reduced rhs of JTE)
+    static constexpr int Wu = Rb + G;             // [G] W_v^T U_v^-1 1             (reduced rhs of the ones vector)
+    static constexpr int Jc = Wu + G;             // [G] rc_v                       (the global JTE)
+    static constexpr int Ab = Jc + G;             //     1^T U_v^-1 rp_v
+    static constexpr int Au = Ab + 1;             //     1^T U_v^-1 1
+    static constexpr int Ng = Au + 1;             //     |G_pose|^2 of the update applied in phase 0
+    static constexpr int Nx = Ng + 1;             //     |x_pose|^2 before it
+    static constexpr int Lc = Nx + 1;
+};
+static_assert(OcLayout<10>::Rb == 55 && OcLayout<10>::Wu == 65 && OcLayout<10>::Jc == 75 && OcLayout<10>::Ab == 85 &&
+                  OcLayout<10>::Nx == 88 && OcLayout<10>::Lc == 89, "contribution layout of calibrate");
+static_assert(OcLayout<26>::Rb == 351 && OcLayout<26>::Wu == 377 && OcLayout<26>::Jc == 403 && OcLayout<26>::Ab == 429 &&
+                  OcLayout<26>::Nx == 432 && OcLayout<26>::Lc == 433, "contribution layout of stereoCalibrate");
 
 constexpr int kOcMaxCorners = 512;   // per view (LDS staging of the 2N x 16 Jacobian strip)
 
@@ -32,25 +40,34 @@ struct OcState {
     double normG2_c, normX2_c;   // intrinsic parts of the last update
     double alpha2, coef;         // alpha_smooth2 and the Sherman-Morrison factor of the pending update
     int pending;       // a pose update waits for the next step's phase 0
-    int error;         // bit 0: a view's 6 x 6 block is not PD, bit 1: the reduced 10 x 10 system
+    int error;         // bit 0: a view's 6 x 6 block is not PD
+};
+
+// What the shared loop (mcc_omnicalib_device.hpp) works on, the same for both kernels; P is the
+// parameter count and G the width of the global block.
+// (st sits behind the buffers: in front, k_os_step keeps the whole leading kernarg tuple in
+// SGPRs from its first st->done test on and spills it around the 26 x 26 elimination.)
+struct OcLoop {
+    double* x;                                 // [P] parameters
+    const double* mask;                        // [G] 1 = free, 0 = fixed (flags2idx / flags2idxStereo)
+    double* Yv;                                // [6 G n] Y_v = U_v^-1 W_v (next step's pose update)
+    double* zb; double* zu;                    // [6n] U_v^-1 rp_v, U_v^-1 1
+    double* yc;                                // [G] global part of the pending solution
+    double* jte;                               // [P] J^T E of the last linearisation
+    double* G;                                 // [P] G of the last update
+    double* contrib;                           // [n * Lc]
+    double* gsum;                              // [n_groups * Lc]
+    int* cnt;                                  // [n_groups + 1] tickets, zero between launches
+    OcState* st;
+    int n, group_size, n_groups;
 };
 
 struct OcArgs {
-    OcState* st;
+    OcLoop lp;                                 // x: [6n + 10] in encodeParameters layout
     const int* view_off;                       // [n+1]
     const double* ox; const double* oy; const double* oz;   // [corners] SoA pattern points
     const double* iu; const double* iv;        // [corners] image points
-    double* x;                                 // [6n + 10] parameters (encodeParameters layout)
-    const double* mask;                        // [10] 1 = free intrinsic, 0 = fixed (flags2idx)
-    double* Yv;                                // [60 n] Y_v = U_v^-1 W_v (next step's pose update)
-    double* zb; double* zu;                    // [6n] U_v^-1 rp_v, U_v^-1 1
-    double* yc;                                // [10] intrinsic part of the pending solution
-    double* jte;                               // [6n + 10] J^T E of the last linearisation
-    double* G;                                 // [6n + 10] G of the last update
-    double* contrib;                           // [n * kOcLc]
-    double* gsum;                              // [n_groups * kOcLc]
-    int* cnt;                                  // [n_groups + 1] tickets, zero between launches
-    int n, group_size, n_groups, max_np;
+    int max_np;
 };
 
 struct OcErrArgs {

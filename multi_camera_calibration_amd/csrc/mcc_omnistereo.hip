@@ -7,8 +7,9 @@
 //   [own pose 6 | om, T 6 | intr_1 10 | intr_2 10]           (32 columns)
 // and the normal matrix is block-arrow: n pose blocks of 6 x 6 and one dense global block of 26.
 //
-// One loop step = one launch of k_os_step, one 256-thread workgroup per view, built like k_oc_step:
-//   phase 0  the pending pose update of this view from the previous step, with its norm partials;
+// One loop step = one launch of k_os_step, one 256-thread workgroup per view.  The loop itself is
+// the shared block-arrow step of mcc_omnicalib_device.hpp with G = 26; this file has what is the
+// two cameras' own:
 //   pose     wave 0: R, Jl of the left pose; wave 1: the composed right pose (device compose(), with
 //            cvRodrigues2's theta ~ pi zeroing of d om3 / d om) and the four chain-rule blocks;
 //   phase A  the corners go through in chunks of 64 or 128: thread (camera, corner) projects with
@@ -17,15 +18,7 @@
 //   phase B  per chunk, the Gram of the left rows (one 16 x 16 tile) and of the right rows (three of
 //            the 2 x 2 tiles) with v_mfma_f64_16x16x4_f64, accumulated in registers over the chunks;
 //            the columns a row half does not touch are never multiplied.  J^T E on the VALU.  The
-//            waves' tiles are summed in wave order into the 32 x 32 strip Gram, fixed intrinsics masked;
-//   phase C  wave 0 inverts the 6 x 6 pose block; the workgroup forms Y = U^-1 W (6 x 26), the Schur
-//            contribution to the 26 x 26 global block (351), the reduced right-hand sides of JTE and
-//            of the ones vector, the Sherman-Morrison scalars and the norms; sc1 write-through, then
-//            the two-level fixed-order last-arriver reduction;
-//   final    stop test, 26 x 26 Gauss-Jordan for both right-hand sides (lane = row, natural-order
-//            positive pivots, else the largest unused entry; singular: G = 0), the rank-one
-//            correction of JTJ + epsilon (:1019), alpha_smooth2, update of the 26 global parameters.
-// FP64 throughout, like the reference.
+//            waves' tiles are summed in wave order into the 32 x 32 strip Gram, fixed intrinsics masked.
 #include <hip/hip_runtime.h>
 
 #include "mcc_device.hpp"
@@ -34,25 +27,12 @@
 
 namespace mcc {
 
-// packed upper-triangle index of (i, j), i <= j, of a 26 x 26 matrix
-__device__ __forceinline__ int os_up(int i, int j) { return i * kOsG - (i * (i - 1)) / 2 + (j - i); }
-
-// oc_sum with the stereo contribution stride
-__device__ __forceinline__ double os_sum(const double* p, int n) {
-    constexpr int B = 16;
-    double v = 0.0;
-    for (int q0 = 0; q0 < n; q0 += B) {
-        double b[B];
-#pragma unroll
-        for (int u = 0; u < B; ++u) b[u] = oc_ld(p + (size_t)min(q0 + u, n - 1) * kOsLc);
-#pragma unroll
-        for (int u = 0; u < B; ++u) v += q0 + u < n ? b[u] : 0.0;
-    }
-    return v;
-}
-
-// index of global-block entry l in the parameter vector
-__device__ __forceinline__ size_t os_gidx(int l, int n) { return l < 6 ? (size_t)l : 6 * (size_t)(n + 1) + (l - 6); }
+// x = [om, T | omL_0, tL_0, ... | intr_1 | intr_2]; the global block is [om, T | intr_1 | intr_2]
+struct OsPos {
+    int n;
+    __device__ size_t pose(int v) const { return 6 + 6 * (size_t)v; }
+    __device__ size_t glob(int l) const { return l < 6 ? (size_t)l : 6 * (size_t)(n + 1) + (l - 6); }
+};
 
 // view pose tables in LDS
 constexpr int kPoseTab = 21;   // R[9], Jl[9], T[3]
@@ -119,10 +99,10 @@ __device__ __forceinline__ void os_right_row(const double* j, const double* ct, 
 }
 
 __global__ __launch_bounds__(256) void k_os_step(OsArgs a) {
-    OcState* st = a.st;
-    if (st->done) return;
+    if (a.lp.st->done) return;
     const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = a.n, np = a.np, ch = a.chunk;
+    const int np = a.np, ch = a.chunk;
+    const OsPos pos{a.lp.n};
     const size_t c0 = (size_t)v * np;
     extern __shared__ double sm[];
     double* JL = sm;                   // [2 ch][16] left rows  [pose 6 | intr_1 10]
@@ -132,32 +112,10 @@ __global__ __launch_bounds__(256) void k_os_step(OsArgs a) {
     double* eR = eL + 2 * ch;          // [2 ch]
     double* Cp = sm;                   // after the last chunk: [4 waves][LL, R00, R01, R11][256]
     double* jp = sm + 4096;            //                       [4 waves][L, R0, R1][64]
-    __shared__ double pose[6], glob[kOsG], msk[kOsG], nrm[2][6], PL[kPoseTab], PR[kPoseTab], CT[kChainTab];
-    __shared__ double C[1024], je[32], je_raw[32], Ui[36], zbl[6], zul[6], Yl[kOsY], tot[kOsLc];
+    __shared__ double pose[6], glob[kOsG], msk[kOsG], nrm[12], PL[kPoseTab], PR[kPoseTab], CT[kChainTab];
+    __shared__ double C[1024], je[32], je_raw[32], Ui[36], zbl[6], zul[6], Yl[6 * kOsG], tot[OcLayout<kOsG>::Lc];
 
-    // ---- phase 0: the pending pose update of the previous step (the kept poses are never fixed)
-    const int pending = st->pending;
-    if (tid < 6) {
-        const size_t xi = 6 + 6 * (size_t)v + tid;
-        const double xo = a.x[xi];
-        double g = 0.0, xn = xo;
-        if (pending) {
-            const double al = st->alpha2, cf = st->coef;
-            double s = 0.0;
-#pragma unroll
-            for (int j = 0; j < kOsG; ++j) s += a.Yv[kOsY * (size_t)v + tid * kOsG + j] * a.yc[j];
-            g = al * ((a.zb[6 * (size_t)v + tid] - cf * a.zu[6 * (size_t)v + tid]) - s);
-            xn = xo + g;
-            a.x[xi] = xn;
-            a.G[xi] = g;
-        }
-        pose[tid] = xn;
-        nrm[0][tid] = g * g;
-        nrm[1][tid] = xo * xo;
-    } else if (tid >= 64 && tid < 64 + kOsG) {
-        glob[tid - 64] = a.x[os_gidx(tid - 64, n)];
-        msk[tid - 64] = a.mask[tid - 64];
-    }
+    const int pending = oc_phase0<kOsG>(a.lp, pos, v, pose, nrm, glob, msk);
     __syncthreads();
 
     // ---- the two poses of the view, once
@@ -309,201 +267,10 @@ __global__ __launch_bounds__(256) void k_os_step(OsArgs a) {
     }
     __syncthreads();
 
-    // ---- phase C: U^-1 (wave 0 register Gauss-Jordan), Schur pieces
-    if (wave == 0) {
-        const int li = lane < 6 ? lane : 0;
-        double row[12];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) { row[j] = C[li * 32 + j]; row[6 + j] = li == j ? 1.0 : 0.0; }
-        double dii = 1.0;
-        bool bad = false;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const double piv = oc_readlane(row[k], k);
-            bad |= !(piv > 0.0);
-            const double pv = piv > 0.0 ? piv : 1.0;
-            const double ip = 1.0 / pv;
-            if (lane == k) dii = pv;
-            const double f = lane == k ? 0.0 : row[k] * ip;
-            double pr[12];
-#pragma unroll
-            for (int j = k + 1; j < 12; ++j) pr[j] = oc_readlane(row[j], k);
-#pragma unroll
-            for (int j = k + 1; j < 12; ++j) row[j] -= f * pr[j];
-        }
-        if (lane < 6) {
-            const double id = 1.0 / dii;
-            double zb = 0.0, zu = 0.0;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const double h = row[6 + j] * id;
-                Ui[lane * 6 + j] = h;
-                zb += h * je[j];
-                zu += h;
-            }
-            zbl[lane] = zb;
-            zul[lane] = zu;
-        }
-        if (bad && lane == 0) atomicOr(&st->error, 1);
-    }
+    oc_pose_inverse<32>(C, je, Ui, zbl, zul, &a.lp.st->error);
     __syncthreads();
-    if (tid < kOsY) {   // Y = U^-1 W (6 x 26), W = C[0:6, 6:32]
-        const int i = tid / kOsG, j = tid % kOsG;
-        double y = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) y += Ui[i * 6 + k] * C[k * 32 + 6 + j];
-        Yl[tid] = y;
-        a.Yv[kOsY * (size_t)v + tid] = y;
-    } else if (tid >= 192 && tid < 198) {
-        a.zb[6 * (size_t)v + tid - 192] = zbl[tid - 192];
-    } else if (tid >= 198 && tid < 204) {
-        a.zu[6 * (size_t)v + tid - 198] = zul[tid - 198];
-    } else if (tid >= 204 && tid < 210) {
-        a.jte[6 + 6 * (size_t)v + tid - 204] = je[tid - 204];
-    }
-    __syncthreads();
-    double* out = a.contrib + (size_t)v * kOsLc;
-    for (int e = tid; e < kOsLc; e += 256) {
-        double s = 0.0;
-        if (e < kOsRb) {
-            int i = 0, rem = e;
-            while (rem >= kOsG - i) { rem -= kOsG - i; ++i; }
-            const int j = i + rem;
-            s = C[(6 + i) * 32 + 6 + j];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) s -= C[k * 32 + 6 + i] * Yl[k * kOsG + j];
-        } else if (e < kOsWu) {
-            const int j = e - kOsRb;
-            s = je[6 + j];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) s -= C[k * 32 + 6 + j] * zbl[k];
-        } else if (e < kOsJc) {
-            const int j = e - kOsWu;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) s += C[k * 32 + 6 + j] * zul[k];
-        } else if (e < kOsAb) {
-            s = je_raw[6 + e - kOsJc];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                s += e == kOsAb ? zbl[k] : e == kOsAu ? zul[k] : e == kOsNg ? nrm[0][k] : nrm[1][k];
-        }
-        oc_st(out + e, s);
-    }
-
-    // ---- two-level fixed-order reduction of the contributions
-    const int grp = v / a.group_size, g0 = grp * a.group_size, gn = min(a.group_size, n - g0);
-    if (!oc_arrive(&a.cnt[grp], gn)) return;
-    for (int e = tid; e < kOsLc; e += 256)
-        oc_st(a.gsum + (size_t)grp * kOsLc + e, os_sum(a.contrib + (size_t)g0 * kOsLc + e, gn));
-    if (!oc_arrive(&a.cnt[a.n_groups], a.n_groups)) return;
-    for (int e = tid; e < kOsLc; e += 256) tot[e] = os_sum(a.gsum + e, a.n_groups);
-    __syncthreads();
-    if (wave != 0) return;
-
-    // ---- final: stop test (:1276-1279), reduced solve, Sherman-Morrison, global update (wave 0)
-    const int k = st->iter;
-    double change = st->change;
-    if (pending) change = sqrt(tot[kOsNg] + st->normG2_c) / sqrt(tot[kOsNx] + st->normX2_c);
-    const int ct = st->crit_type;
-    const bool stop = (ct == 1 && k >= st->max_count) || (ct == 2 && change <= st->eps) ||
-                      (ct == 3 && (change <= st->eps || k >= st->max_count));
-    if (lane == 0) st->change = change;
-    if (stop) {
-        if (lane == 0) { st->done = 1; st->pending = 0; }
-        return;
-    }
-    const double alpha2 = 1.0 - pow(1.0 - 0.01, (double)k + 1.0);   // alpha_smooth2 (:1280)
-    const double epsilon = 0.01 * pow(0.9, (double)k / 10);          // (:1282)
-    const int li = lane < kOsG ? lane : 0;
-    const bool free_i = msk[li] != 0.0;
-    double row[kOsG + 2];
-#pragma unroll
-    for (int j = 0; j < kOsG; ++j) {
-        const double sv = tot[kOsS + (li <= j ? os_up(li, j) : os_up(j, li))];
-        row[j] = free_i ? sv : (j == li ? 1.0 : 0.0);
-    }
-    row[kOsG] = free_i ? tot[kOsRb + li] : 0.0;
-    row[kOsG + 1] = free_i ? 1.0 - tot[kOsWu + li] : 0.0;
-    // Gauss-Jordan, lane l keeps row l, as k_oc_step's 10 x 10: the diagonal in natural order while
-    // it is positive, else the unused row of largest |entry|; an exactly singular system gives
-    // G = 0 for the whole step, as the reference's Mat::inv() (DECOMP_LU) returns a zero matrix then
-    bool used = lane >= kOsG, singular = false;
-    int pcol = -1;
-    double dii = 1.0;
-#pragma unroll
-    for (int kk = 0; kk < kOsG; ++kk) {
-        int pl = kk;
-        if (!(oc_readlane(row[kk], kk) > 0.0) || __builtin_amdgcn_readlane((int)used, kk) != 0) {
-            pl = -1;
-            double best = 0.0;
-#pragma nounroll
-            for (int l = 0; l < kOsG; ++l) {
-                const double c = fabs(oc_readlane(row[kk], l));
-                const bool u = __builtin_amdgcn_readlane((int)used, l) != 0;
-                if (!u && c > best) { best = c; pl = l; }
-            }
-            if (pl < 0) { singular = true; break; }
-        }
-        const double piv = oc_readlane(row[kk], pl);
-        const double ip = 1.0 / piv;
-        if (lane == pl) { dii = piv; used = true; pcol = kk; }
-        const double f = lane == pl ? 0.0 : row[kk] * ip;
-        double pr[kOsG + 2];
-#pragma unroll
-        for (int j = kk + 1; j < kOsG + 2; ++j) pr[j] = oc_readlane(row[j], pl);
-#pragma unroll
-        for (int j = kk + 1; j < kOsG + 2; ++j) row[j] -= f * pr[j];
-    }
-    // lane j takes the solution of column j from the lane that pivoted it
-    const double sb = lane < kOsG && !singular ? row[kOsG] / dii : 0.0;
-    const double su = lane < kOsG && !singular ? row[kOsG + 1] / dii : 0.0;
-    double yb = 0.0, yu = 0.0;
-#pragma nounroll
-    for (int j = 0; j < kOsG; ++j) {
-        const unsigned long long own = __ballot(pcol == j);
-        const int src = own ? (int)__builtin_ctzll(own) : 0;
-        const double vb = oc_readlane(sb, src), vu = oc_readlane(su, src);
-        if (lane == j) { yb = vb; yu = vu; }
-    }
-    // 1^T A^-1 b = sum_v 1^T U^-1 rp_v - (sum_v W_v^T U^-1 1)^T yb + 1_free^T yb (and for u)
-    const double wm = lane < kOsG ? msk[lane] - tot[kOsWu + lane] : 0.0;
-    double s1 = tot[kOsAb], s2 = tot[kOsAu];
-#pragma unroll
-    for (int l = 0; l < kOsG; ++l) {
-        s1 += oc_readlane(wm * yb, l);
-        s2 += oc_readlane(wm * yu, l);
-    }
-    double coef = epsilon * s1 / (1.0 + epsilon * s2);
-    // A + epsilon 1 1^T singular (Sherman-Morrison denominator 0) or A singular: G = 0 for the step
-    const bool skip = singular || !isfinite(coef);
-    if (skip) coef = 0.0;
-    const double yc = skip ? 0.0 : yb - coef * yu;
-    const double a2 = skip ? 0.0 : alpha2;
-    const double gc = a2 * yc;
-    double ng = 0.0, nx = 0.0;
-    double xo = 0.0;
-    if (lane < kOsG) {
-        const size_t gi = os_gidx(lane, n);
-        xo = a.x[gi];
-        a.x[gi] = xo + gc;
-        a.yc[lane] = yc;
-        a.G[gi] = gc;
-        a.jte[gi] = tot[kOsJc + lane];
-    }
-#pragma unroll
-    for (int l = 0; l < kOsG; ++l) {
-        ng += oc_readlane(gc * gc, l);
-        nx += oc_readlane(xo * xo, l);
-    }
-    if (lane == 0) {
-        st->normG2_c = ng;
-        st->normX2_c = nx;
-        st->alpha2 = a2;   // 0: the poses' pending G is 0 too
-        st->coef = coef;
-        st->pending = 1;
-        st->iter = k + 1;
-    }
+    oc_contribute<kOsG, 32>(a.lp, pos, v, C, je, je_raw, Ui, zbl, zul, nrm, Yl);
+    oc_reduce_solve<kOsG>(a.lp, pos, v, pending, msk, tot);
 }
 
 // estimateUncertaintiesStereo's squared reprojection errors of both cameras, per view (:1826-1864)
@@ -546,7 +313,7 @@ hipError_t mcc_os_set_attrs(int chunk) {
 }
 
 hipError_t mcc_launch_os_step(const mcc::OsArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(mcc::k_os_step, dim3(a.n), dim3(256), mcc_os_shmem(a.chunk), s, a);
+    hipLaunchKernelGGL(mcc::k_os_step, dim3(a.lp.n), dim3(256), mcc_os_shmem(a.chunk), s, a);
     return hipGetLastError();
 }
 

@@ -17,24 +17,21 @@
 #include "mcc_omnicalib_host.hpp"
 #include "mcc_omnistereo_internal.h"
 
-using mcc::OcState;
+struct mcc_omnistereo : OcHandle {
+    static constexpr int kG = mcc::kOsG;
+    static constexpr const char* kName = "omnidir stereoCalibrate";
+    static constexpr const char* kStepName = "k_os_step";
+    int np = 0, chunk = 64;
+    DBuf<double> ox, oy, oz, iu1, iv1, iu2, iv2;
 
-struct mcc_omnistereo {
-    int n = 0, np = 0, P = 0, flags = 0, device = 0, chunk = 64, group_size = 1, n_groups = 1;
-    long long corners = 0;
-    hipStream_t stream = nullptr;
-    DBuf<double> ox, oy, oz, iu1, iv1, iu2, iv2, x, mask, Yv, zb, zu, yc, jte, G, contrib, gsum, view_sq;
-    DBuf<int> cnt;
-    DBuf<OcState> st;
-    OcState* h_st = nullptr;
-    static constexpr int kGraphSteps = 8;
-    hipGraphExec_t gexec[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-
-    mcc::OsArgs args() const {
-        return mcc::OsArgs{st.p, ox.p, oy.p, oz.p, iu1.p, iv1.p, iu2.p, iv2.p, x.p, mask.p, Yv.p, zb.p, zu.p, yc.p,
-                           jte.p, G.p, contrib.p, gsum.p, cnt.p, n, np, chunk, group_size, n_groups};
+    hipError_t launch_step() const {
+        return mcc_launch_os_step(mcc::OsArgs{loop(), ox.p, oy.p, oz.p, iu1.p, iv1.p, iu2.p, iv2.p, np, chunk}, stream);
     }
+    hipError_t launch_err() const {
+        return mcc_launch_os_err(
+            mcc::OsErrArgs{ox.p, oy.p, oz.p, iu1.p, iv1.p, iu2.p, iv2.p, x.p, view_sq.p, n, np}, stream);
+    }
+    double rms_points() const { return 2.0 * (double)corners; }   // both cameras' points (:1880-1888)
 };
 
 namespace {
@@ -56,74 +53,6 @@ int os_check_views(int n, const int* off, int* np_out) {
     }
     *np_out = np;
     return MCC_OK;
-}
-
-int os_set_state(mcc_omnistereo* h, int iter, int crit, int max_count, double eps) {
-    OCCHK(hipStreamSynchronize(h->stream));
-    OcState s{};
-    s.iter = iter;
-    s.crit_type = crit;
-    s.max_count = max_count;
-    s.eps = eps;
-    s.change = 1.0;
-    *h->h_st = s;
-    OCCHK(hipMemcpyAsync(h->st.p, h->h_st, sizeof(OcState), hipMemcpyHostToDevice, h->stream));
-    OCCHK(hipStreamSynchronize(h->stream));
-    return MCC_OK;
-}
-
-int os_read_state(mcc_omnistereo* h) {
-    OCCHK(hipMemcpyAsync(h->h_st, h->st.p, sizeof(OcState), hipMemcpyDeviceToHost, h->stream));
-    OCCHK(hipStreamSynchronize(h->stream));
-    if (h->h_st->error & 1)
-        return oc_fail(MCC_ENOTPD, "omnidir stereoCalibrate: a view's 6x6 pose block J^T J is not positive definite");
-    return MCC_OK;
-}
-
-int os_upload_params(mcc_omnistereo* h, const double* params) {
-    OCCHK(hipMemcpyAsync(h->x.p, params, sizeof(double) * h->P, hipMemcpyHostToDevice, h->stream));
-    return MCC_OK;
-}
-
-int os_build_graphs(mcc_omnistereo* h) {
-    if (h->gexec[0]) return MCC_OK;
-    const int counts[2] = {1, mcc_omnistereo::kGraphSteps};
-    const mcc::OsArgs a = h->args();
-    for (int g = 0; g < 2; ++g) {   // linear chains of 1 and 8 steps
-        hipGraph_t graph;
-        OCCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        hipError_t le = hipSuccess;
-        for (int s = 0; s < counts[g] && le == hipSuccess; ++s) le = mcc_launch_os_step(a, h->stream);
-        hipError_t ee = hipStreamEndCapture(h->stream, &graph);
-        if (le != hipSuccess) return oc_fail(MCC_EHIP, std::string("k_os_step launch: ") + hipGetErrorString(le));
-        if (ee != hipSuccess) return oc_fail(MCC_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ee));
-        OCCHK(hipGraphInstantiate(&h->gexec[g], graph, nullptr, nullptr, 0));
-        OCCHK(hipGraphDestroy(graph));
-    }
-    return MCC_OK;
-}
-
-int os_launch_steps(mcc_omnistereo* h, int n) {
-    int rc = os_build_graphs(h);
-    if (rc) return rc;
-    while (n >= mcc_omnistereo::kGraphSteps) {
-        OCCHK(hipGraphLaunch(h->gexec[1], h->stream));
-        n -= mcc_omnistereo::kGraphSteps;
-    }
-    while (n-- > 0) OCCHK(hipGraphLaunch(h->gexec[0], h->stream));
-    return MCC_OK;
-}
-
-void rodrigues_host(const double* om, double* R) {   // cvRodrigues2 vector -> matrix
-    const double th = std::sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    std::copy(I, I + 9, R);
-    if (th < 2.220446049250313e-16) return;
-    const double c = std::cos(th), s = std::sin(th), c1 = 1 - c;
-    const double x = om[0] / th, y = om[1] / th, z = om[2] / th;
-    const double rrt[9] = {x * x, x * y, x * z, x * y, y * y, y * z, x * z, y * z, z * z};
-    const double rx[9] = {0, -z, y, z, 0, -x, -y, x, 0};
-    for (int k = 0; k < 9; ++k) R[k] = c * I[k] + c1 * rrt[k] + s * rx[k];
 }
 
 // findMedian (:2172-2181) with its even and odd cases as the reference has them: an even count
@@ -156,159 +85,46 @@ int mcc_omnistereo_create(mcc_omnistereo** out, const mcc_omnistereo_desc* d) {
     h->device = d->device;
     h->chunk = np <= 64 ? 64 : 128;
     h->corners = (long long)n * np;
-    h->group_size = std::max(1, (int)std::ceil(std::sqrt((double)n)));
-    h->n_groups = (n + h->group_size - 1) / h->group_size;
-    auto bail = [&](int code) {
+    rc = [&] {
+        OCCHK(hipSetDevice(d->device));
+        OCCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        const size_t C = (size_t)h->corners;
+        OCCHK(oc_upload_soa(d->obj, 3, C, {&h->ox, &h->oy, &h->oz}));
+        OCCHK(oc_upload_soa(d->img1, 2, C, {&h->iu1, &h->iv1}));
+        OCCHK(oc_upload_soa(d->img2, 2, C, {&h->iu2, &h->iv2}));
+        double m[mcc::kOsG];
+        for (int k = 0; k < 6; ++k) m[k] = 1.0;   // om, T and the kept poses are never fixed
+        intrinsic_mask(d->flags, m + 6);
+        std::copy(m + 6, m + 16, m + 16);
+        OCCHK(h->mask.upload(m, mcc::kOsG));
+        OCCHK(mcc_os_set_attrs(h->chunk));
+        return oc_alloc_loop(h);
+    }();
+    if (rc) {
         mcc_omnistereo_destroy(h);
-        return code;
-    };
-#define OSCHK_H(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) return bail(oc_fail(MCC_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
-    } while (0)
-    OSCHK_H(hipSetDevice(d->device));
-    OSCHK_H(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    const size_t C = (size_t)h->corners;
-    std::vector<double> soa[7];
-    for (auto& s : soa) s.resize(C);
-    for (size_t c = 0; c < C; ++c) {
-        soa[0][c] = d->obj[3 * c];
-        soa[1][c] = d->obj[3 * c + 1];
-        soa[2][c] = d->obj[3 * c + 2];
-        soa[3][c] = d->img1[2 * c];
-        soa[4][c] = d->img1[2 * c + 1];
-        soa[5][c] = d->img2[2 * c];
-        soa[6][c] = d->img2[2 * c + 1];
+        return rc;
     }
-    DBuf<double>* pts[7] = {&h->ox, &h->oy, &h->oz, &h->iu1, &h->iv1, &h->iu2, &h->iv2};
-    for (int k = 0; k < 7; ++k) OSCHK_H(pts[k]->upload(soa[k].data(), C));
-    double m[mcc::kOsG];
-    for (int k = 0; k < 6; ++k) m[k] = 1.0;   // om, T and the kept poses are never fixed
-    intrinsic_mask(d->flags, m + 6);
-    std::copy(m + 6, m + 16, m + 16);
-    OSCHK_H(h->mask.upload(m, mcc::kOsG));
-    OSCHK_H(h->x.alloc(h->P));
-    OSCHK_H(h->Yv.alloc(mcc::kOsY * (size_t)n));
-    OSCHK_H(h->zb.alloc(6 * (size_t)n));
-    OSCHK_H(h->zu.alloc(6 * (size_t)n));
-    OSCHK_H(h->yc.alloc(mcc::kOsG));
-    OSCHK_H(h->jte.alloc(h->P));
-    OSCHK_H(h->G.alloc(h->P));
-    OSCHK_H(h->contrib.alloc((size_t)n * mcc::kOsLc));
-    OSCHK_H(h->gsum.alloc((size_t)h->n_groups * mcc::kOsLc));
-    OSCHK_H(h->view_sq.alloc(n));
-    OSCHK_H(h->cnt.alloc(h->n_groups + 1));
-    OSCHK_H(hipMemset(h->cnt.p, 0, sizeof(int) * (h->n_groups + 1)));
-    OSCHK_H(hipMemset(h->G.p, 0, sizeof(double) * h->P));
-    OSCHK_H(hipMemset(h->jte.p, 0, sizeof(double) * h->P));
-    OSCHK_H(h->st.alloc(1));
-    OSCHK_H(hipHostMalloc((void**)&h->h_st, sizeof(OcState), hipHostMallocDefault));
-    OSCHK_H(mcc_os_set_attrs(h->chunk));
-    OSCHK_H(hipEventCreate(&h->ev[0]));
-    OSCHK_H(hipEventCreate(&h->ev[1]));
-#undef OSCHK_H
     *out = h;
     return MCC_OK;
 }
 
-void mcc_omnistereo_destroy(mcc_omnistereo* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto& g : h->gexec)
-        if (g) (void)hipGraphExecDestroy(g);
-    for (auto& e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (DBuf<double>* b : {&h->ox, &h->oy, &h->oz, &h->iu1, &h->iv1, &h->iu2, &h->iv2, &h->x, &h->mask, &h->Yv,
-                            &h->zb, &h->zu, &h->yc, &h->jte, &h->G, &h->contrib, &h->gsum, &h->view_sq})
-        b->release();
-    h->cnt.release();
-    h->st.release();
-    if (h->h_st) (void)hipHostFree(h->h_st);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void mcc_omnistereo_destroy(mcc_omnistereo* h) { oc_destroy(h); }
 
 int mcc_omnistereo_nparams(const mcc_omnistereo* h) { return h ? h->P : MCC_EINVAL; }
 
 int mcc_omnistereo_jacobian(mcc_omnistereo* h, const double* params, int iter, double* jte, double* G) {
-    if (!h || !params || iter < 0) return oc_fail(MCC_EINVAL, "bad argument");
-    OCCHK(hipSetDevice(h->device));
-    int rc = os_set_state(h, iter, MCC_CRIT_COUNT, iter + 1, 0.0);
-    if (rc) return rc;
-    if ((rc = os_upload_params(h, params))) return rc;
-    // step 1 linearises and solves iteration `iter` (the global part of G), step 2 applies the
-    // pending pose update (the pose part of G) and stops (iter + 1 >= max_count); JTE is read
-    // between the two, because step 2 linearises again at the updated point
-    const mcc::OsArgs a = h->args();
-    OCCHK(mcc_launch_os_step(a, h->stream));
-    if ((rc = os_read_state(h))) return rc;
-    if (jte) OCCHK(hipMemcpy(jte, h->jte.p, sizeof(double) * h->P, hipMemcpyDeviceToHost));
-    OCCHK(mcc_launch_os_step(a, h->stream));
-    if ((rc = os_read_state(h))) return rc;
-    if (G) OCCHK(hipMemcpy(G, h->G.p, sizeof(double) * h->P, hipMemcpyDeviceToHost));
-    return MCC_OK;
+    return oc_jacobian(h, params, iter, jte, G);
 }
 
 int mcc_omnistereo_optimize(mcc_omnistereo* h, int crit_type, int max_count, double eps, double* params_inout,
                             int* iters, double* last_change) {
-    if (!h || !params_inout) return oc_fail(MCC_EINVAL, "null argument");
-    if (crit_type < 1 || crit_type > 3) return oc_fail(MCC_EINVAL, "crit_type must be 1, 2 or 3");
-    OCCHK(hipSetDevice(h->device));
-    int rc = os_set_state(h, 0, crit_type, max_count, eps);
-    if (rc) return rc;
-    if ((rc = os_upload_params(h, params_inout))) return rc;
-    const long long cap = crit_type == MCC_CRIT_EPS ? 1000000LL : (long long)max_count + 1;
-    long long launched = 0;
-    while (true) {
-        if ((rc = os_launch_steps(h, mcc_omnistereo::kGraphSteps))) return rc;
-        launched += mcc_omnistereo::kGraphSteps;
-        if ((rc = os_read_state(h))) return rc;
-        if (h->h_st->done) break;
-        if (launched > cap + mcc_omnistereo::kGraphSteps)
-            return oc_fail(MCC_EINVAL, "omnidir stereoCalibrate did not terminate");
-    }
-    if (iters) *iters = h->h_st->iter;
-    if (last_change) *last_change = h->h_st->change;
-    OCCHK(hipMemcpy(params_inout, h->x.p, sizeof(double) * h->P, hipMemcpyDeviceToHost));
-    return MCC_OK;
+    return oc_optimize(h, crit_type, max_count, eps, params_inout, iters, last_change);
 }
 
-int mcc_omnistereo_rms(mcc_omnistereo* h, const double* params, double* rms) {
-    if (!h || !params || !rms) return oc_fail(MCC_EINVAL, "null argument");
-    OCCHK(hipSetDevice(h->device));
-    OCCHK(hipStreamSynchronize(h->stream));
-    int rc = os_upload_params(h, params);
-    if (rc) return rc;
-    const mcc::OsErrArgs a{h->ox.p, h->oy.p, h->oz.p, h->iu1.p, h->iv1.p, h->iu2.p, h->iv2.p, h->x.p, h->view_sq.p,
-                           h->n, h->np};
-    OCCHK(mcc_launch_os_err(a, h->stream));
-    std::vector<double> sq(h->n);
-    OCCHK(hipMemcpyAsync(sq.data(), h->view_sq.p, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    OCCHK(hipStreamSynchronize(h->stream));
-    double s = 0;
-    for (int v = 0; v < h->n; ++v) s += sq[v];   // view order
-    *rms = std::sqrt(s / (2.0 * (double)h->corners));   // over both cameras' points (:1880-1888)
-    return MCC_OK;
-}
+int mcc_omnistereo_rms(mcc_omnistereo* h, const double* params, double* rms) { return oc_rms(h, params, rms); }
 
 int mcc_omnistereo_time_steps(mcc_omnistereo* h, const double* params, int n_steps, double* ms_per_step) {
-    if (!h || !params || n_steps < 1 || !ms_per_step) return oc_fail(MCC_EINVAL, "bad argument");
-    OCCHK(hipSetDevice(h->device));
-    int rc = os_set_state(h, 0, 0, 0, 0.0);
-    if (rc) return rc;
-    if ((rc = os_upload_params(h, params))) return rc;
-    if ((rc = os_launch_steps(h, 2))) return rc;   // graph instantiation + first touch
-    OCCHK(hipEventRecord(h->ev[0], h->stream));
-    if ((rc = os_launch_steps(h, n_steps))) return rc;
-    OCCHK(hipEventRecord(h->ev[1], h->stream));
-    OCCHK(hipEventSynchronize(h->ev[1]));
-    if ((rc = os_read_state(h))) return rc;
-    float ms = 0.f;
-    OCCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    *ms_per_step = (double)ms / n_steps;
-    return MCC_OK;
+    return oc_time_steps(h, params, n_steps, ms_per_step);
 }
 
 int mcc_omnidir_stereo_encode_init(int n1, const int* idx1, const double* om1, const double* t1, int n2,
