@@ -737,6 +737,23 @@ __device__ __forceinline__ void fold_final(const LinArgs& la) {
 #ifndef MCC_GROUP_OCC
 #define MCC_GROUP_OCC 2   // k_group workgroups per CU the register budget allows (LDS: ~64 KB each)
 #endif
+// Issue priority inside the edge round, 32 lanes per edge only (two waves per SIMD: waves w and w + 4).  The
+// round is bound by VALU issue and the SIMD's older wave (0..3) wins the arbitration, so the younger one
+// ends the round ~6.7 k cycles later, alone on the SIMD for most of that.  Waves
+// 4..7 take priority 1 for a part of the round and every wave is back at 0 before the round's end:
+//   0 never   1 the whole round   2 from the sweep's start   3 from the butterfly on
+#ifndef MCC_EDGE_PRIO
+#define MCC_EDGE_PRIO 2
+#endif
+template <int L, int AT>
+__device__ __forceinline__ void edge_prio_up() {
+    // (the readfirstlane makes the branch scalar; on the plain thread index s_setprio is issued by every wave)
+    if (L == 32 && MCC_EDGE_PRIO == AT && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
+}
+template <int L>
+__device__ __forceinline__ void edge_prio_down() {
+    if (L == 32 && MCC_EDGE_PRIO != 0) __builtin_amdgcn_s_setprio(0);
+}
 // The group's work (phases 0, A, B above); false when the loop has stopped (nothing done).
 template <int MODEL, bool RATIONAL, int PRISM, bool BACK, int L>
 __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
@@ -758,6 +775,9 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
     const int C = a.n_cams, m = a.global_dim;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const GroupLayout GL = group_layout(gne, C, nq, nc);
+#ifdef MCC_DIAG
+    long long wt0 = 0, wt1 = 0, wt2 = 0, wt3 = 0;   // this wave's round-0 stamps (WSTAMP)
+#endif
     double* rec = smem + GL.rec;
     double* s27 = smem + GL.s27;
     double* sLi = smem + GL.sLi;
@@ -1027,6 +1047,7 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
     }
     __syncthreads();
     SSTAMP(stp, 2, 0);
+    WSTAMP(wt0);
     // the first round's corners (phase 0's last loads) -> this wave's staging; the prologue's last
     // wave_sync_lds orders these stores ahead of the sweep's reads
     stage_store(cv0, sb0, cn0);
@@ -1039,6 +1060,7 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
         const int cam = info.x;
         double* P = sP + kGRecP * es;
         double* Gbe = sGb + 56 * es;
+        edge_prio_up<L, 1>();
         if (rb > 0 && ev) stage(info.z, 0, min(info.w, kGChunk));
         if (ev) {
             group_prologue<MODEL, BACK, L>(sph + 24 * seq[le], ctab + 24 * cam, sds, info.y, sub, rec + kGRec * le, P, Gbe);
@@ -1047,6 +1069,8 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
         }
         wave_sync_lds();
         if (rb == 0) SSTAMP(stp, 3, 0);
+        if (rb == 0) WSTAMP(wt1);
+        edge_prio_up<L, 2>();
         // ---- the sweep (k_edge's): FP64 projection + 2 x 6 J' rows, float32 residual, 27 sums
         double acc[32];
 #pragma unroll
@@ -1108,6 +1132,8 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
         }
         // ---- butterfly (k_edge's strided reduce-scatter over the edge's 16 lanes), then the chain
         if (rb == 0) SSTAMP(stp, 4, 0);
+        if (rb == 0) WSTAMP(wt2);
+        edge_prio_up<L, 3>();
         int tq = lane;
         asm volatile("" : "+v"(tq));
         strided_reduce_scatter<L>(acc, tq);
@@ -1135,13 +1161,21 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
             group_chain(sCH[gq], sGb + 56 * (wave * EPW + gq), sq, eq < gne, rec + kGRec * (eq < gne ? eq : 0));
         }
         wave_sync_lds();   // this wave's chain records are consumed before the next round's corners
+        edge_prio_down<L>();
         if (rb == 0) SSTAMP(stp, 5, 0);
+        if (rb == 0) WSTAMP(wt3);
     }
 #ifdef MCC_DIAG
     if (stp && lane == 0 && wave < 16) {   // per wave: the rounds done (slots 16 + wave)
         __builtin_amdgcn_sched_barrier(0);
         stp[16 + wave] = (long long)MCC_DIAG_CLOCK();
         __builtin_amdgcn_sched_barrier(0);
+    }
+    // per wave, round 0: the ends of its prologue, sweep and chain as cycles since the barrier that ends
+    // phase 0, 21 bits each (slots 24 + wave; tools/diag_split.py prints them per wave half)
+    if (stp && lane == 0 && wave < 8) {
+        const long long m21 = (1ll << 21) - 1;
+        stp[24 + wave] = ((wt1 - wt0) & m21) | (((wt2 - wt0) & m21) << 21) | (((wt3 - wt0) & m21) << 42);
     }
 #endif
     __syncthreads();

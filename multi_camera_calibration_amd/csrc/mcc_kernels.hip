@@ -84,6 +84,17 @@ namespace mcc {
 #else
 #define SSTAMP(ptr, k, who) do { } while (0)
 #endif
+// the clock into a variable of the calling wave (every wave stamps; k_group's per-wave round-0 stamps)
+#ifdef MCC_DIAG
+#define WSTAMP(v)                                                                                  \
+    do {                                                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+        v = (long long)MCC_DIAG_CLOCK();                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+    } while (0)
+#else
+#define WSTAMP(v) do { } while (0)
+#endif
 // chip-wide 100 MHz clock (s_memtime is per XCD): cross-workgroup timelines
 #ifdef MCC_DIAG
 #define RSTAMP(k)                                                                                  \

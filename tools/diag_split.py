@@ -5,7 +5,9 @@ diagnostic build (libmcc_diag.so).  Never quote this build's run time: read its 
     MCC_LIB=multi_camera_calibration_amd/libmcc_diag.so python tools/diag_split.py [config] [views]
 
 k_group (the split step's group kernel) group g -> row g slots 0..10 (start, loads, photo update and
-Rodrigues, round 0's prologue, sweep, chain, the later rounds, Hpp sums, Cholesky, U / Y', pairs).
+Rodrigues, round 0's prologue, sweep, chain, the later rounds, Hpp sums, Cholesky, U / Y', pairs), all
+stamped by wave 0; slots 16 + w wave w's last round's end and 24 + w its round-0 prologue, sweep and chain
+ends, printed per wave half (wave_halves).
 Otherwise rows of the stamp buffer (32 slots each): k_photo photo p -> row p slots 0..5 (start, staged,
 Cholesky, U / Y', pairs stored; slot 2 unused); k_prep workgroup w -> row w slots 8..11 (start, update,
 photo Rodrigues, edges stored); k_edge workgroup w -> row w / 2 slots 16 + 8 (w & 1) + 0..4
@@ -23,6 +25,38 @@ from multi_camera_calibration_amd import api, rig  # noqa: E402
 def med(v):
     v = v[v > 0]
     return f"median {np.median(v):8.0f}  p90 {np.percentile(v, 90):8.0f}  (n={len(v)})" if len(v) else "n/a"
+
+
+def wave_halves(rows, ng):
+    """k_group's per-wave round-0 stamps: slot 24 + w holds wave w's prologue, sweep and chain ends as
+    cycles since the barrier that ends phase 0 (21 bits each), slot 16 + w its last round's end.  With 32
+    lanes per edge waves w and w + 4 share a SIMD: printed per half, with the per-group gap between the
+    halves' last waves."""
+    rows = rows[:ng].astype(np.int64)
+    nw = int(np.count_nonzero(rows[0, 24:32]))
+    if nw == 0:
+        return
+    m21 = (1 << 21) - 1
+    pk = rows[:, 24:24 + nw]
+    pro, swp, chn = pk & m21, (pk >> 21) & m21, (pk >> 42) & m21
+    end = rows[:, 16:16 + nw] - rows[:, 2:3]   # wave 0's stamp 2 stands for every wave's (same barrier)
+    halves = [("waves 0-3", slice(0, 4)), ("waves 4-7", slice(4, 8))] if nw == 8 else [(f"waves 0-{nw - 1}", slice(0, nw))]
+    print(f"k_group round 0 per wave, cycles since the end of phase 0 ({nw} waves; median over groups of the half's "
+          "mean, [min wave, max wave])")
+    for name, sl in halves:
+        print(f"  {name}")
+        for lab, v in (("prologue end", pro), ("sweep end", swp), ("chain end", chn), ("rounds end", end)):
+            h = v[:, sl]
+            print(f"    {lab:14s} {np.median(h.mean(axis=1)):8.0f}  [{np.median(h.min(axis=1)):8.0f}, "
+                  f"{np.median(h.max(axis=1)):8.0f}]")
+        d = np.diff(np.stack([np.zeros_like(pro[:, sl]), pro[:, sl], swp[:, sl], chn[:, sl]]), axis=0)
+        print("    durations      prologue %.0f  sweep %.0f  butterfly+chain %.0f" %
+              tuple(np.median(d[k].mean(axis=1)) for k in range(3)))
+    if nw == 8:
+        gap = end[:, 4:8].max(axis=1) - end[:, 0:4].max(axis=1)
+        print(f"  last wave of 4-7 minus last wave of 0-3: median {np.median(gap):.0f}  p10 {np.percentile(gap, 10):.0f}  "
+              f"p90 {np.percentile(gap, 90):.0f}")
+        print(f"  last wave's rounds end (stamp 2 -> all waves at the barrier): median {np.median(end.max(axis=1)):.0f}")
 
 
 def main():
@@ -55,6 +89,7 @@ def main():
         phases(list(range(11)), ["loads (round trip 1)", "photo update+Rodrigues", "edge prologue (r0)", "sweep (r0)",
                                  "butterfly+chain (r0)", "later rounds", "photo Hpp sums", "Cholesky", "U, Y'",
                                  "pairs+store"], f"k_group ({ng} groups)")
+        wave_halves(raw[:32 * nv].reshape(nv, 32), ng)
         return
     phases([0, 1, 3, 4, 5], ["load+stage+sums", "Cholesky, Li", "U, Y'", "pairs+store"], "k_photo")
     phases([8, 9, 10, 11], ["photo update", "photo Rodrigues", "edge prologues"], "k_prep")

@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Static instruction counts of k_group's edge round from a device-only assembly listing (CPU only):
+
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -DMCC_PART=3 --cuda-device-only -S \
+        multi_camera_calibration_amd/csrc/mcc_kernels.hip -o part3.s
+    python3 tools/edge_round_counts.py part3.s [mangled-name substring] [--hist]
+
+The default kernel is the omnidirectional one at 32 lanes per edge (config4's).  Regions, in the
+listing's own order (blocks the compiler moved behind the kernel's end, the cold loops, are not counted):
+  prologue   from the third s_barrier (the end of phase 0) to the head of the sweep loop
+  sweep      the loop body: the innermost loop with the most FP64 instructions
+  chain      from the sweep loop's end to the next s_barrier (butterfly, record scatter, chain)
+Per region: VALU instructions, the FP64 ones among them, moves, selects and the remaining (integer,
+address, lane-crossing) VALU; --hist adds the FP64 opcode histogram, which a bit-neutral change must
+leave equal.  The kernel's VGPR count and SGPR spill count come from the listing's metadata."""
+import collections
+import re
+import sys
+
+DEFAULT = "k_groupILi1ELb0ELi0ELb0ELi32ELb0E"
+
+
+def kernel_text(lines, pat):
+    start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\S*" + re.escape(pat) + r"\S*:", l))
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    return lines[start:end]
+
+
+def op_of(line):
+    t = line.split(";")[0].strip()
+    if not t or t.endswith(":") or t.startswith("."):
+        return None
+    return t.split()[0]
+
+
+def classify(ops):
+    c = collections.Counter()
+    for o in ops:
+        if not o.startswith("v_"):
+            continue
+        c["valu"] += 1
+        if "_f64" in o:
+            c["fp64"] += 1
+        elif o.startswith("v_mov_b") or o.startswith("v_accvgpr"):
+            c["mov"] += 1
+        elif o.startswith("v_cndmask"):
+            c["select"] += 1
+        elif "permlane" in o or "readlane" in o or "writelane" in o or "readfirstlane" in o or "_dpp" in o:
+            c["lane"] += 1
+        else:
+            c["other"] += 1
+    return c
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    hist = "--hist" in sys.argv
+    lines = open(args[0]).read().splitlines()
+    pat = args[1] if len(args) > 1 else DEFAULT
+    k = kernel_text(lines, pat)
+    ops = [op_of(l) for l in k]
+    bars = [i for i, o in enumerate(ops) if o == "s_barrier"]
+    labels = {l.split(":")[0]: i for i, l in enumerate(k) if re.match(r"^\.LBB\d+_\d+:", l)}
+    # the loops (backward branches) between the third and the fourth barrier; the sweep is the innermost
+    # one (no other loop inside it) with the most FP64 instructions
+    assert len(bars) > 3, "k_group has at least four barriers"
+    loops = []
+    for i in range(bars[2], bars[3]):
+        m = re.match(r"\s+s_cbranch_\S+\s+(\.LBB\d+_\d+)", k[i])
+        if m and m.group(1) in labels and labels[m.group(1)] < i:
+            loops.append((labels[m.group(1)], i))
+    inner = [(h, e) for h, e in loops if not any((h2, e2) != (h, e) and h <= h2 and e2 <= e for h2, e2 in loops)]
+    lh, le = max(inner, key=lambda r: sum(1 for o in ops[r[0]:r[1]] if o and o.startswith("v_") and "_f64" in o))
+    b0, b1 = bars[2], bars[3]
+    regions = [("prologue", b0, lh), ("sweep body", lh, le + 1), ("chain", le + 1, b1)]
+    print(f"kernel {pat}: {len(k)} listing lines, edge round between the barriers at lines {b0} and {b1}, sweep loop {lh}..{le}")
+    print(f"{'region':12s} {'VALU':>6s} {'FP64':>6s} {'mov':>6s} {'select':>6s} {'lane':>6s} {'other':>6s} {'SALU':>6s} {'LDS':>6s}")
+    for name, a, b in regions:
+        r = [o for o in ops[a:b] if o]
+        c = classify(r)
+        salu = sum(1 for o in r if o.startswith("s_") and not o.startswith(("s_waitcnt", "s_nop", "s_barrier")))
+        lds = sum(1 for o in r if o.startswith("ds_"))
+        print(f"{name:12s} {c['valu']:6d} {c['fp64']:6d} {c['mov']:6d} {c['select']:6d} {c['lane']:6d} {c['other']:6d} {salu:6d} {lds:6d}")
+        if hist:
+            h = collections.Counter(o for o in r if o.startswith("v_") and "_f64" in o)
+            print("   FP64: " + "  ".join(f"{o} {n}" for o, n in sorted(h.items())))
+            h = collections.Counter(o for o in r if o.startswith("v_") and "_f64" not in o)
+            print("   rest: " + "  ".join(f"{o} {n}" for o, n in h.most_common()))
+    meta = "\n".join(lines)
+    for key in ("num_vgpr", "numbered_sgpr", "private_seg_size"):
+        m = re.search(re.escape(pat) + r"\S*\." + key + r", (\d+)", meta)
+        if m:
+            print(key, m.group(1))
+    sp = [l for l in k if "v_writelane_b32" in l]
+    rl = [l for l in k if "v_readlane_b32" in l]
+    print(f"whole kernel: v_writelane_b32 {len(sp)}  v_readlane_b32 {len(rl)} (SGPR spills and reloads)")
+
+
+if __name__ == "__main__":
+    main()
