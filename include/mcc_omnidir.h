@@ -31,6 +31,16 @@
  *                                 (:2078-2170), and one G of the loop (:1280-1290).
  *   mcc_omnistereo_optimize ..... the loop of stereoCalibrate (:1274-1301), on the device.
  *   mcc_omnistereo_rms .......... estimateUncertaintiesStereo's rms (:1826-1888).
+ *   mcc_omnidir_undistort_points  cv::omnidir::undistortPoints (:249-343), on the device.
+ *   mcc_omnidir_init_undistort_rectify_map  cv::omnidir::initUndistortRectifyMap (:348-533), on the
+ *                                 device, all four RECTIFY_* flags, float or fixed-point maps.
+ *   mcc_omnidir_remap ........... the cv::remap call of undistortImage (:545): INTER_LINEAR,
+ *                                 BORDER_CONSTANT, fixed-point maps, 8-bit images.
+ *   mcc_omnidir_undistort_image . cv::omnidir::undistortImage (:538-546).
+ *   mcc_omnidir_stereo_rectify .. cv::omnidir::stereoRectify (:2190-2227); host code, no GPU.
+ *   mcc_omnirect_create ......... the maps of undistortImage (:543-544), built once and kept on the
+ *                                 device for a stream of frames.
+ *   mcc_omnirect_remap .......... its remap (:545) of one frame.
  *
  * Parameters use the reference's encodeParameters layout (src/omnidir.cpp:1541-1568), CV_64F:
  *   x = [om_0(3), T_0(3), ..., om_{n-1}, T_{n-1}, fx, fy, s, cx, cy, xi, k1, k2, p1, p2], P = 6n + 10.
@@ -180,6 +190,88 @@ int mcc_omnidir_stereo_calibrate(int n_views, const int *view_off, const double 
                                  int crit_type, int max_count, double eps, int device, double *K1, double *xi1,
                                  double *D1, double *K2, double *xi2, double *D2, double *om, double *T, double *omL,
                                  double *tL, int *idx, int *n_idx, double *rms, int *iters);
+
+/* ---------------------------------------------------------------- rectification of points and images
+ * cv::omnidir::undistortPoints (:249-343), initUndistortRectifyMap (:348-533), undistortImage
+ * (:538-546) and stereoRectify (:2190-2227).  K, R, P, Knew are 3 x 3 row-major (of a 3 x 4 P pass
+ * the first three columns), D = (k1, k2, p1, p2); NULL stands for the reference's empty array:
+ * R = identity, D = 0, P / Knew = K.  Images are 8-bit, 1 or 3 interleaved channels, with a row
+ * stride in bytes; bytes of a destination row past width * channels are never written.
+ *
+ * A fixed-point map pair is OpenCV's CV_16SC2 + CV_16UC1: with iu = cvRound(32 u), iv = cvRound(32 v)
+ * map1 = ((short)(iu >> 5), (short)(iv >> 5)) -- the cast wraps -- and map2 = (iv & 31) * 32 + (iu & 31);
+ * 32 u outside the int range (or NaN) is unspecified, as in the reference.  The remap is cv::remap
+ * with INTER_LINEAR and BORDER_CONSTANT 0 on such maps: fx = map2 & 31, fy = (map2 >> 5) & 31, the
+ * tap weights (32 - fx)(32 - fy) 32, fx (32 - fy) 32, (32 - fx) fy 32, fx fy 32, a tap outside the
+ * source reads 0, dst = (sum + 16384) >> 15.
+ *
+ * Bad arguments (a null required pointer, n < 0, a size that is not positive or above 32767, channels
+ * other than 1 or 3, a stride shorter than a row, an unknown flag or map type, a singular P R, P or
+ * R) are MCC_EINVAL before any device work. */
+
+/* cv::omnidir::RECTIFY_* (include/opencv2/ccalib/omnidir.hpp:68-73) */
+#define MCC_OMNI_RECTIFY_PERSPECTIVE 1
+#define MCC_OMNI_RECTIFY_CYLINDRICAL 2
+#define MCC_OMNI_RECTIFY_LONGLATI 3
+#define MCC_OMNI_RECTIFY_STEREOGRAPHIC 4
+
+#define MCC_OMNI_MAP_FLOAT 1   /* CV_32FC1: map1 = (float)u, map2 = (float)v            */
+#define MCC_OMNI_MAP_FIXED 2   /* CV_16SC2 + CV_16UC1, see above                         */
+
+/* undistortPoints: n pixels (u, v) -> X/Z, Y/Z of their rays after R; n == 0 touches nothing. */
+int mcc_omnidir_undistort_points(int n, const double *distorted, const double *K, const double *D, double xi,
+                                 const double *R, int device, double *undistorted);
+
+/* stereoRectify (host, no GPU): R1 with rows e1 = T21 / |T21|, e2 = (-T21.y, T21.x, 0) / |.|,
+ * e3 = e1 x e2 / |.| for T21 = -R^T T, and R2 = R1 R^T.  T = 0, or T21 along z (the reference's
+ * 0 / 0), is MCC_EINVAL. */
+int mcc_omnidir_stereo_rectify(const double *R, const double *T, double *R1, double *R2);
+
+/* initUndistortRectifyMap: MCC_OMNI_MAP_FLOAT writes two float[width * height],
+ * MCC_OMNI_MAP_FIXED short[2 * width * height] and unsigned short[width * height]. */
+int mcc_omnidir_init_undistort_rectify_map(const double *K, const double *D, double xi, const double *R,
+                                           const double *P, int width, int height, int map_type, int flags,
+                                           int device, void *map1, void *map2);
+
+/* the remap of undistortImage with host fixed-point maps (short[2 * dst_w * dst_h],
+ * unsigned short[dst_w * dst_h]) */
+int mcc_omnidir_remap(const unsigned char *src, int src_w, int src_h, int channels, long long src_stride,
+                      const short *map1, const unsigned short *map2, int dst_w, int dst_h,
+                      unsigned char *dst, long long dst_stride, int device);
+
+/* undistortImage in one call; the maps never leave the device.  new_w == 0 takes the source
+ * size. */
+int mcc_omnidir_undistort_image(const unsigned char *src, int src_w, int src_h, int channels, long long src_stride,
+                                const double *K, const double *D, double xi, int flags, const double *Knew,
+                                int new_w, int new_h, const double *R, int device, unsigned char *dst,
+                                long long dst_stride);
+
+/* The per-frame case: the fixed-point maps are built once at create and stay on the device with
+ * the source and destination images; every remap call is one upload, one kernel, one download. */
+typedef struct mcc_omnirect mcc_omnirect;
+
+typedef struct mcc_omnirect_desc {
+    const double *K;       /* [9]                                                 */
+    const double *D;       /* [4] or NULL                                         */
+    double xi;
+    const double *R;       /* [9] or NULL                                         */
+    const double *P;       /* [9] or NULL (Knew of undistortImage)                */
+    int flags;             /* MCC_OMNI_RECTIFY_*                                  */
+    int dst_width, dst_height;
+    int src_width, src_height;
+    int channels;          /* 1 or 3                                              */
+    int device;            /* HIP device ordinal                                  */
+} mcc_omnirect_desc;
+
+int mcc_omnirect_create(mcc_omnirect **out, const mcc_omnirect_desc *desc);
+void mcc_omnirect_destroy(mcc_omnirect *h);
+int mcc_omnirect_remap(mcc_omnirect *h, const unsigned char *src, long long src_stride, unsigned char *dst,
+                       long long dst_stride);
+
+/* measurement, as mcc_omnicalib_time_steps: n_frames back-to-back remap launches on the resident
+ * source (whatever the last remap left there); ms_per_frame = device time per launch from two HIP
+ * events on the handle's stream. */
+int mcc_omnirect_time_remap(mcc_omnirect *h, int n_frames, double *ms_per_frame);
 
 #ifdef __cplusplus
 }

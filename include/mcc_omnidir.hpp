@@ -1,6 +1,7 @@
 /*
- * mcc_omnidir.hpp -- C++ mirror of cv::omnidir::calibrate and cv::omnidir::stereoCalibrate (below)
- * over the C ABI (mcc_omnidir.h):
+ * mcc_omnidir.hpp -- C++ mirror of cv::omnidir::calibrate, cv::omnidir::stereoCalibrate and the
+ * rectification calls undistortPoints / initUndistortRectifyMap / undistortImage / stereoRectify
+ * (all below) over the C ABI (mcc_omnidir.h).  calibrate has
  * the same name, argument order and meaning as include/opencv2/ccalib/omnidir.hpp's
  *
  *   double calibrate(InputArrayOfArrays objectPoints, InputArrayOfArrays imagePoints, Size size,
@@ -17,6 +18,7 @@
 #ifndef MCC_OMNIDIR_HPP
 #define MCC_OMNIDIR_HPP
 
+#include <algorithm>
 #include <array>
 #include <stdexcept>
 #include <string>
@@ -24,6 +26,7 @@
 
 #include "mcc_multicalib.hpp"
 #include "mcc_omnidir.h"
+#include "mcc_pnp.hpp"
 
 namespace mcc {
 namespace omnidir {
@@ -144,6 +147,127 @@ inline double stereoCalibrate(const std::vector<std::vector<Vec3d>>& objectPoint
         }
     if (idx) idx->assign(kept.begin(), kept.begin() + nk);
     return rms;
+}
+
+/*
+ * cv::omnidir::undistortPoints (src/omnidir.cpp:249-343), initUndistortRectifyMap (:348-533),
+ * undistortImage (:538-546) and stereoRectify (:2190-2227): the same names, argument order and
+ * meaning as include/opencv2/ccalib/omnidir.hpp, with std containers and an Image view in place of
+ * cv::Mat.  A rotation R is a 3 x 3 matrix (9 values) or a rotation vector (3 values, converted with
+ * mcc::pnp::rodrigues of libmcc_host.so) or empty (identity); P / Knew is 3 x 3 (9 values), 3 x 4
+ * (12 values, its first three columns are taken) or empty (K); D may be empty (zero) where the
+ * reference allows it.  Wrong sizes throw std::invalid_argument, everything the C ABI refuses or
+ * the device fails at std::runtime_error with mcc_last_error().
+ */
+enum {
+    RECTIFY_PERSPECTIVE = MCC_OMNI_RECTIFY_PERSPECTIVE,
+    RECTIFY_CYLINDRICAL = MCC_OMNI_RECTIFY_CYLINDRICAL,
+    RECTIFY_LONGLATI = MCC_OMNI_RECTIFY_LONGLATI,
+    RECTIFY_STEREOGRAPHIC = MCC_OMNI_RECTIFY_STEREOGRAPHIC
+};
+enum { MAP_32FC1 = MCC_OMNI_MAP_FLOAT, MAP_16SC2 = MCC_OMNI_MAP_FIXED };   // m1type
+
+// an 8-bit image of 1 or 3 interleaved channels; step is the row stride in bytes (0: packed rows)
+struct Image {
+    unsigned char* data = nullptr;
+    int width = 0, height = 0, channels = 1;
+    long long step = 0;
+    long long stride() const { return step ? step : (long long)width * channels; }
+};
+
+namespace detail {
+
+// empty -> null; 9 values as they are; 3 values -> Rodrigues
+inline const double* rotation(const std::vector<double>& R, std::array<double, 9>& buf, const char* who) {
+    if (R.empty()) return nullptr;
+    if (R.size() == 3)
+        pnp::rodrigues(R.data(), buf.data());
+    else if (R.size() == 9)
+        std::copy(R.begin(), R.end(), buf.begin());
+    else
+        throw std::invalid_argument(std::string(who) + ": R must hold 9 values (3 x 3) or 3 (a rotation vector)");
+    return buf.data();
+}
+
+// empty -> null; 3 x 3 as it is; 3 x 4 -> its first three columns
+inline const double* projection(const std::vector<double>& P, std::array<double, 9>& buf, const char* who) {
+    if (P.empty()) return nullptr;
+    if (P.size() != 9 && P.size() != 12)
+        throw std::invalid_argument(std::string(who) + ": P must hold 9 values (3 x 3) or 12 (3 x 4)");
+    const size_t cols = P.size() / 3;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) buf[3 * r + c] = P[cols * r + c];
+    return buf.data();
+}
+
+inline const double* distortion(const std::vector<double>& D, const char* who) {
+    if (D.empty()) return nullptr;
+    if (D.size() != 4) throw std::invalid_argument(std::string(who) + ": D must hold 4 values (k1, k2, p1, p2)");
+    return D.data();
+}
+
+}  // namespace detail
+
+inline void undistortPoints(const std::vector<Vec2d>& distorted, std::vector<Vec2d>& undistorted,
+                            const std::array<double, 9>& K, const std::array<double, 4>& D, double xi,
+                            const std::vector<double>& R = {}, int device = 0) {
+    std::array<double, 9> Rb{};
+    const double* Rp = detail::rotation(R, Rb, "omnidir::undistortPoints");
+    undistorted.assign(distorted.size(), Vec2d{});
+    const int rc = mcc_omnidir_undistort_points((int)distorted.size(), distorted.empty() ? nullptr : distorted[0].data(),
+                                                K.data(), D.data(), xi, Rp, device,
+                                                undistorted.empty() ? nullptr : undistorted[0].data());
+    if (rc != MCC_OK) throw std::runtime_error(std::string("omnidir::undistortPoints: ") + mcc_last_error());
+}
+
+// m1type MAP_16SC2: map1 holds short[2 w h], map2 unsigned short[w h]; MAP_32FC1: both hold float[w h].
+// The maps are returned as raw bytes of those types.
+inline void initUndistortRectifyMap(const std::array<double, 9>& K, const std::vector<double>& D, double xi,
+                                    const std::vector<double>& R, const std::vector<double>& P, Size size, int m1type,
+                                    std::vector<unsigned char>& map1, std::vector<unsigned char>& map2, int flags,
+                                    int device = 0) {
+    const char* who = "omnidir::initUndistortRectifyMap";
+    std::array<double, 9> Rb{}, Pb{};
+    const double* Rp = detail::rotation(R, Rb, who);
+    const double* Pp = detail::projection(P, Pb, who);
+    const double* Dp = detail::distortion(D, who);
+    if (m1type <= 0) m1type = MAP_16SC2;   // as the reference (:352)
+    const size_t px = size.width > 0 && size.height > 0 ? (size_t)size.width * size.height : 0;
+    map1.assign(std::max<size_t>(px * 4, 1), 0);
+    map2.assign(std::max<size_t>(px * (m1type == MAP_32FC1 ? 4 : 2), 1), 0);
+    const int rc = mcc_omnidir_init_undistort_rectify_map(K.data(), Dp, xi, Rp, Pp, size.width, size.height, m1type,
+                                                          flags, device, map1.data(), map2.data());
+    if (rc != MCC_OK) throw std::runtime_error(std::string(who) + ": " + mcc_last_error());
+}
+
+// undistorted must point at new_size (or, with an empty new_size, distorted's size) pixels of
+// distorted's channel count
+inline void undistortImage(const Image& distorted, const Image& undistorted, const std::array<double, 9>& K,
+                           const std::vector<double>& D, double xi, int flags, const std::vector<double>& Knew = {},
+                           Size new_size = Size(), const std::vector<double>& R = {}, int device = 0) {
+    const char* who = "omnidir::undistortImage";
+    std::array<double, 9> Rb{}, Pb{};
+    const double* Rp = detail::rotation(R, Rb, who);
+    const double* Pp = detail::projection(Knew, Pb, who);
+    const double* Dp = detail::distortion(D, who);
+    const bool keep = new_size.width <= 0 || new_size.height <= 0;   // Size::empty()
+    const int w = keep ? distorted.width : new_size.width, h = keep ? distorted.height : new_size.height;
+    if (undistorted.width != w || undistorted.height != h || undistorted.channels != distorted.channels)
+        throw std::invalid_argument(std::string(who) + ": the destination must be " + std::to_string(w) + " x " +
+                                    std::to_string(h) + " with the source's channels");
+    const int rc = mcc_omnidir_undistort_image(distorted.data, distorted.width, distorted.height, distorted.channels,
+                                               distorted.stride(), K.data(), Dp, xi, flags, Pp, w, h, Rp, device,
+                                               undistorted.data, undistorted.stride());
+    if (rc != MCC_OK) throw std::runtime_error(std::string(who) + ": " + mcc_last_error());
+}
+
+inline void stereoRectify(const std::vector<double>& R, const Vec3d& T, std::array<double, 9>& R1,
+                          std::array<double, 9>& R2) {
+    std::array<double, 9> Rb{};
+    const double* Rp = detail::rotation(R, Rb, "omnidir::stereoRectify");
+    if (!Rp) throw std::invalid_argument("omnidir::stereoRectify: R must hold 9 values (3 x 3) or 3 (a rotation vector)");
+    if (mcc_omnidir_stereo_rectify(Rp, T.data(), R1.data(), R2.data()) != MCC_OK)
+        throw std::runtime_error(std::string("omnidir::stereoRectify: ") + mcc_last_error());
 }
 
 }  // namespace omnidir

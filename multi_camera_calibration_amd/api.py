@@ -29,6 +29,9 @@ HEADERS = [HEADER, os.path.join(os.path.dirname(_HERE), "include", "mcc_omnidir.
 _i32p = ctypes.POINTER(ctypes.c_int)
 _f32p = ctypes.POINTER(ctypes.c_float)
 _f64p = ctypes.POINTER(ctypes.c_double)
+_u8p = ctypes.POINTER(ctypes.c_ubyte)
+_i16p = ctypes.POINTER(ctypes.c_short)
+_u16p = ctypes.POINTER(ctypes.c_ushort)
 
 MCC_CRIT_COUNT, MCC_CRIT_EPS, MCC_CRIT_COUNT_EPS = 1, 2, 3
 
@@ -54,6 +57,13 @@ class _OmniDesc(ctypes.Structure):
 class _OmniStereoDesc(ctypes.Structure):
     _fields_ = [("n_views", ctypes.c_int), ("view_off", _i32p), ("obj", _f64p), ("img1", _f64p), ("img2", _f64p),
                 ("flags", ctypes.c_int), ("device", ctypes.c_int)]
+
+
+class _OmniRectDesc(ctypes.Structure):
+    _fields_ = [("K", _f64p), ("D", _f64p), ("xi", ctypes.c_double), ("R", _f64p), ("P", _f64p),
+                ("flags", ctypes.c_int), ("dst_width", ctypes.c_int), ("dst_height", ctypes.c_int),
+                ("src_width", ctypes.c_int), ("src_height", ctypes.c_int), ("channels", ctypes.c_int),
+                ("device", ctypes.c_int)]
 
 
 _LIB = None
@@ -164,6 +174,27 @@ def lib():
             _f64p, _i32p, _i32p]
         L.mcc_omnidir_stereo_calibrate.argtypes = [ctypes.c_int, _i32p, _f64p, _f64p, _f64p] + [ctypes.c_int] * 7 + [
             ctypes.c_double, ctypes.c_int] + [_f64p] * 10 + [_i32p, _i32p, _f64p, _i32p]
+        # (the rectification entry points: absent from an older build loaded through MCC_LIB for an A/B)
+        _ll = ctypes.c_longlong
+        for name, args in (
+                ("mcc_omnidir_undistort_points", [ctypes.c_int, _f64p, _f64p, _f64p, ctypes.c_double, _f64p, ctypes.c_int,
+                                                  _f64p]),
+                ("mcc_omnidir_stereo_rectify", [_f64p] * 4),
+                ("mcc_omnidir_init_undistort_rectify_map", [_f64p, _f64p, ctypes.c_double, _f64p, _f64p] +
+                 [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2),
+                ("mcc_omnidir_remap", [_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ll, _i16p, _u16p, ctypes.c_int,
+                                       ctypes.c_int, _u8p, _ll, ctypes.c_int]),
+                ("mcc_omnidir_undistort_image", [_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ll, _f64p, _f64p,
+                                                 ctypes.c_double, ctypes.c_int, _f64p, ctypes.c_int, ctypes.c_int, _f64p,
+                                                 ctypes.c_int, _u8p, _ll]),
+                ("mcc_omnirect_create", [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_OmniRectDesc)]),
+                ("mcc_omnirect_destroy", [ctypes.c_void_p]),
+                ("mcc_omnirect_remap", [ctypes.c_void_p, _u8p, _ll, _u8p, _ll]),
+                ("mcc_omnirect_time_remap", [ctypes.c_void_p, ctypes.c_int, _f64p])):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = args
+        if hasattr(L, "mcc_omnirect_destroy"):
+            L.mcc_omnirect_destroy.restype = None
         _LIB = L
     return _LIB
 
@@ -695,3 +726,166 @@ def omnidir_stereo_calibrate(off, obj, img1, img2, image_size1, image_size2, fla
     k = nk.value
     return (rms.value, K1.reshape(3, 3), float(xi1[0]), D1, K2.reshape(3, 3), float(xi2[0]), D2, om, T, omL[:k],
             tL[:k], idx[:k].copy(), it.value)
+
+
+# ---------------------------------------------------------------- cv::omnidir rectification
+# include/mcc_omnidir.h; the reference's names: cv::omnidir::undistortPoints (src/omnidir.cpp:249-343),
+# initUndistortRectifyMap (:348-533), undistortImage (:538-546), stereoRectify (:2190-2227).
+RECTIFY_PERSPECTIVE, RECTIFY_CYLINDRICAL, RECTIFY_LONGLATI, RECTIFY_STEREOGRAPHIC = 1, 2, 3, 4
+MAP_FLOAT, MAP_FIXED = 1, 2
+
+
+def _mat3(a, what, vector_ok=False):
+    """None, a 3 x 3 matrix (or the first three columns of a 3 x 4 one), or a rotation vector."""
+    if a is None:
+        return None
+    a = np.asarray(a, np.float64)
+    if vector_ok and a.size == 3:
+        return np.ascontiguousarray(_rig.rodrigues(a.reshape(3)))
+    if a.shape == (3, 4):
+        a = a[:, :3]
+    if a.size != 9:
+        raise MccError(f"{what} must be 3 x 3")
+    return np.ascontiguousarray(a.reshape(3, 3))
+
+
+def _vec(a, n, what):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    if a.size != n:
+        raise MccError(f"{what} must hold {n} values")
+    return a
+
+
+def _image(img, what):
+    """uint8 [h, w] or [h, w, c] with contiguous pixels (rows may be strided): (array, w, h, c, stride)."""
+    if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise MccError(f"{what} must be a uint8 array [h, w] or [h, w, channels]")
+    c = 1 if img.ndim == 2 else img.shape[2]
+    if img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != c) or img.strides[0] < 0:
+        img = np.ascontiguousarray(img)
+    return img, img.shape[1], img.shape[0], c, img.strides[0]
+
+
+def omnidir_undistort_points(distorted, K, D, xi, R=None, device=0):
+    """cv::omnidir::undistortPoints: pixels [n, 2] -> X/Z, Y/Z [n, 2] of their rays after R (a 3 x 3
+    matrix or a rotation vector)."""
+    pts = np.ascontiguousarray(distorted, np.float64).reshape(-1, 2)
+    K, D, R = _mat3(K, "K"), _vec(D, 4, "D"), _mat3(R, "R", True)
+    out = np.zeros_like(pts)
+    _check(lib().mcc_omnidir_undistort_points(pts.shape[0], _ptr(pts, _f64p), _ptr(K, _f64p), _ptr(D, _f64p),
+                                              float(xi), _ptr(R, _f64p), device, _ptr(out, _f64p)),
+           "mcc_omnidir_undistort_points")
+    return out
+
+
+def omnidir_stereo_rectify(R, T):
+    """cv::omnidir::stereoRectify: (R1, R2) of the rig whose second camera is at (R, T) -- host code, no GPU."""
+    R, T = _mat3(R, "R", True), _vec(T, 3, "T")
+    R1, R2 = np.zeros((3, 3)), np.zeros((3, 3))
+    _check(lib().mcc_omnidir_stereo_rectify(_ptr(R, _f64p), _ptr(T, _f64p), _ptr(R1, _f64p), _ptr(R2, _f64p)),
+           "mcc_omnidir_stereo_rectify")
+    return R1, R2
+
+
+def omnidir_init_undistort_rectify_map(K, D, xi, R, P, size, map_type=MAP_FIXED, flags=RECTIFY_PERSPECTIVE, device=0):
+    """cv::omnidir::initUndistortRectifyMap for size = (width, height): MAP_FLOAT gives two float32
+    [h, w] maps (u, v), MAP_FIXED int16 [h, w, 2] and uint16 [h, w] (CV_16SC2 + CV_16UC1)."""
+    K, D, R, P = _mat3(K, "K"), _vec(D, 4, "D"), _mat3(R, "R", True), _mat3(P, "P")
+    w, h = int(size[0]), int(size[1])
+    shape = (max(h, 0), max(w, 0))
+    if map_type == MAP_FLOAT:
+        m1, m2 = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+    else:
+        m1, m2 = np.zeros(shape + (2,), np.int16), np.zeros(shape, np.uint16)
+    _check(lib().mcc_omnidir_init_undistort_rectify_map(_ptr(K, _f64p), _ptr(D, _f64p), float(xi), _ptr(R, _f64p),
+                                                        _ptr(P, _f64p), w, h, map_type, flags, device,
+                                                        m1.ctypes.data_as(ctypes.c_void_p),
+                                                        m2.ctypes.data_as(ctypes.c_void_p)),
+           "mcc_omnidir_init_undistort_rectify_map")
+    return m1, m2
+
+
+def _dst_image(dst, w, h, c, squeeze):
+    if dst is None:
+        dst = np.zeros((h, w) if squeeze else (h, w, c), np.uint8)
+    d, dw, dh, dc, stride = _image(dst, "dst")
+    if d is not dst or (dw, dh, dc) != (w, h, c):
+        raise MccError(f"dst must be a uint8 array of {h} x {w} x {c} with contiguous pixels")
+    return dst, stride
+
+
+def omnidir_remap(src, map1, map2, dst=None, device=0):
+    """cv::remap(src, map1, map2, INTER_LINEAR, BORDER_CONSTANT) for fixed-point maps (int16 [h, w, 2],
+    uint16 [h, w]) and a uint8 image of 1 or 3 channels.  A given dst (rows may be strided) is written
+    in place: only width * channels bytes of each row."""
+    src, sw, sh, c, sstride = _image(src, "src")
+    map1, map2 = np.ascontiguousarray(map1, np.int16), np.ascontiguousarray(map2, np.uint16)
+    if map1.ndim != 3 or map1.shape[2] != 2 or map2.shape != map1.shape[:2]:
+        raise MccError("map1 must be int16 [h, w, 2] and map2 uint16 [h, w]")
+    h, w = map2.shape
+    dst, dstride = _dst_image(dst, w, h, c, src.ndim == 2)
+    _check(lib().mcc_omnidir_remap(_ptr(src, _u8p), sw, sh, c, sstride, _ptr(map1, _i16p), _ptr(map2, _u16p), w, h,
+                                   _ptr(dst, _u8p), dstride, device), "mcc_omnidir_remap")
+    return dst
+
+
+def omnidir_undistort_image(src, K, D, xi, flags, Knew=None, new_size=None, R=None, dst=None, device=0):
+    """cv::omnidir::undistortImage: the fixed-point maps and the remap in one call; new_size =
+    (width, height), None for the source size."""
+    src, sw, sh, c, sstride = _image(src, "src")
+    K, D, Knew, R = _mat3(K, "K"), _vec(D, 4, "D"), _mat3(Knew, "Knew"), _mat3(R, "R", True)
+    w, h = (sw, sh) if new_size is None else (int(new_size[0]), int(new_size[1]))
+    dst, dstride = _dst_image(dst, w, h, c, src.ndim == 2)
+    _check(lib().mcc_omnidir_undistort_image(_ptr(src, _u8p), sw, sh, c, sstride, _ptr(K, _f64p), _ptr(D, _f64p),
+                                             float(xi), flags, _ptr(Knew, _f64p), w, h, _ptr(R, _f64p), device,
+                                             _ptr(dst, _u8p), dstride), "mcc_omnidir_undistort_image")
+    return dst
+
+
+class OmniRectifier:
+    """The per-frame case of undistortImage (mcc_omnirect): the fixed-point maps of (K, D, xi, R, P,
+    flags) for dst_size are built once and stay on the device with the two images."""
+
+    def __init__(self, K, D, xi, flags, src_size, channels=1, P=None, dst_size=None, R=None, device=0):
+        self._keep = [_mat3(K, "K"), _vec(D, 4, "D"), _mat3(R, "R", True), _mat3(P, "P")]
+        self.src_size = (int(src_size[0]), int(src_size[1]))
+        self.dst_size = self.src_size if dst_size is None else (int(dst_size[0]), int(dst_size[1]))
+        self.channels = int(channels)
+        d = _OmniRectDesc()
+        d.K, d.D, d.R, d.P = (_ptr(a, _f64p) for a in self._keep)
+        d.xi, d.flags, d.device = float(xi), flags, device
+        d.dst_width, d.dst_height = self.dst_size
+        d.src_width, d.src_height = self.src_size
+        d.channels = self.channels
+        h = ctypes.c_void_p()
+        _check(lib().mcc_omnirect_create(ctypes.byref(h), ctypes.byref(d)), "mcc_omnirect_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcc_omnirect_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def remap(self, src, dst=None):
+        """One frame (uint8 [h, w] or [h, w, channels] of src_size) through the resident maps."""
+        src, sw, sh, c, sstride = _image(src, "src")
+        if (sw, sh) != self.src_size or c != self.channels:
+            raise MccError(f"src must be {self.src_size[1]} x {self.src_size[0]} x {self.channels}")
+        dst, dstride = _dst_image(dst, self.dst_size[0], self.dst_size[1], c, src.ndim == 2)
+        _check(lib().mcc_omnirect_remap(self.h, _ptr(src, _u8p), sstride, _ptr(dst, _u8p), dstride),
+               "mcc_omnirect_remap")
+        return dst
+
+    def time_remap(self, n_frames):
+        """Device milliseconds per frame over n_frames back-to-back remap launches on the resident source."""
+        ms = ctypes.c_double(0)
+        _check(lib().mcc_omnirect_time_remap(self.h, int(n_frames), ctypes.byref(ms)), "mcc_omnirect_time_remap")
+        return ms.value
