@@ -5,7 +5,8 @@
  * doubleSide.hpp:133-164) can be declared with its own signatures, and a subclass written the way
  * the reference writes MyMultiCameraCalibration / DoubleSideCalibration compiles against it.
  *
- * What it is: a reference-counted 2-D matrix of CV_32F / CV_64F elements (1-4 channels), with
+ * What it is: a reference-counted 2-D matrix of CV_32F / CV_64F elements, or CV_8U for images (any
+ * channel count; stereoReconstruct's cloud has 6), with
  * OpenCV's header semantics (copies share data; clone() deep-copies; rowRange / colRange / row /
  * col are views into the parent), element access (at, ptr), convertTo, t(), matrix products,
  * element-wise + / -, scalar scaling and cv::norm.  Type codes follow OpenCV (CV_32F = 5,
@@ -29,13 +30,17 @@
 #endif
 
 #ifndef MCC_HAVE_OPENCV
+#define CV_8U 0
 #define CV_32F 5
 #define CV_64F 6
 #define CV_CN_SHIFT 3
 #define CV_MAKETYPE(depth, cn) ((depth) + (((cn)-1) << CV_CN_SHIFT))
+#define CV_8UC1 CV_MAKETYPE(CV_8U, 1)
+#define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
 #define CV_32FC2 CV_MAKETYPE(CV_32F, 2)
 #define CV_32FC3 CV_MAKETYPE(CV_32F, 3)
+#define CV_32FC(n) CV_MAKETYPE(CV_32F, (n))
 #define CV_64FC1 CV_MAKETYPE(CV_64F, 1)
 #define CV_64FC2 CV_MAKETYPE(CV_64F, 2)
 #define CV_64FC3 CV_MAKETYPE(CV_64F, 3)
@@ -77,7 +82,8 @@ public:
 
     void create(int r, int c, int type) {
         if (r < 0 || c < 0) throw std::invalid_argument("cv::Mat: negative size");
-        if ((type & 7) != CV_32F && (type & 7) != CV_64F) throw std::invalid_argument("cv::Mat: CV_32F / CV_64F only");
+        if ((type & 7) != CV_32F && (type & 7) != CV_64F && (type & 7) != CV_8U)
+            throw std::invalid_argument("cv::Mat: CV_8U / CV_32F / CV_64F only");
         rows = r;
         cols = c;
         type_ = type;
@@ -88,7 +94,7 @@ public:
     int type() const { return type_; }
     int depth() const { return type_ & 7; }
     int channels() const { return 1 + (type_ >> CV_CN_SHIFT); }
-    size_t elemSize1() const { return depth() == CV_64F ? 8 : 4; }
+    size_t elemSize1() const { return depth() == CV_64F ? 8 : depth() == CV_32F ? 4 : 1; }
     size_t elemSize() const { return elemSize1() * channels(); }
     size_t total() const { return (size_t)rows * cols; }
     bool empty() const { return total() == 0; }
@@ -116,20 +122,22 @@ public:
     }
 
     // element (r, c) of a single-channel matrix as double, whatever the depth
-    double get(int r, int c) const {
-        return depth() == CV_64F ? (double)ptr<double>(r)[c] : (double)ptr<float>(r)[c];
+    double get(int r, int c) const { return scalar(r, c); }
+    void set(int r, int c, double v) { put(r, c, v); }
+    // scalar c of row r (c runs over cols * channels) as double, whatever the depth; a CV_8U store
+    // rounds to nearest even and saturates, as OpenCV's saturate_cast does
+    double scalar(int r, int c) const {
+        return depth() == CV_64F ? ptr<double>(r)[c] : depth() == CV_32F ? (double)ptr<float>(r)[c] : (double)ptr<unsigned char>(r)[c];
     }
-    void set(int r, int c, double v) {
+    void put(int r, int c, double v) {
         if (depth() == CV_64F) ptr<double>(r)[c] = v;
-        else ptr<float>(r)[c] = (float)v;
+        else if (depth() == CV_32F) ptr<float>(r)[c] = (float)v;
+        else ptr<unsigned char>(r)[c] = (unsigned char)std::min(255.0, std::max(0.0, std::nearbyint(v)));
     }
     Mat& setTo(double v) {
         const int cn = channels();
         for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < cols * cn; ++c) {
-                if (depth() == CV_64F) ptr<double>(r)[c] = v;
-                else ptr<float>(r)[c] = (float)v;
-            }
+            for (int c = 0; c < cols * cn; ++c) put(r, c, v);
         return *this;
     }
 
@@ -172,11 +180,7 @@ public:
         const int cn = channels();
         Mat out(rows, cols, CV_MAKETYPE(rtype & 7, cn));
         for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < cols * cn; ++c) {
-                const double v = alpha * (depth() == CV_64F ? ptr<double>(r)[c] : (double)ptr<float>(r)[c]);
-                if (out.depth() == CV_64F) out.ptr<double>(r)[c] = v;
-                else out.ptr<float>(r)[c] = (float)v;
-            }
+            for (int c = 0; c < cols * cn; ++c) out.put(r, c, alpha * scalar(r, c));
         dst = out;
     }
     // a continuous matrix with cn channels and r rows over the same data (OpenCV's reshape)
@@ -254,11 +258,7 @@ private:
         Mat m(rows, cols, type_);
         const int cn = channels();
         for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < cols * cn; ++c) {
-                const double v = depth() == CV_64F ? ptr<double>(r)[c] : (double)ptr<float>(r)[c];
-                if (depth() == CV_64F) m.ptr<double>(r)[c] = f(v);
-                else m.ptr<float>(r)[c] = (float)f(v);
-            }
+            for (int c = 0; c < cols * cn; ++c) m.put(r, c, f(scalar(r, c)));
         return m;
     }
     template <typename F>
@@ -267,12 +267,7 @@ private:
         Mat m(rows, cols, type_);
         const int cn = channels();
         for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < cols * cn; ++c) {
-                const double x = depth() == CV_64F ? ptr<double>(r)[c] : (double)ptr<float>(r)[c];
-                const double y = depth() == CV_64F ? b.ptr<double>(r)[c] : (double)b.ptr<float>(r)[c];
-                if (depth() == CV_64F) m.ptr<double>(r)[c] = f(x, y);
-                else m.ptr<float>(r)[c] = (float)f(x, y);
-            }
+            for (int c = 0; c < cols * cn; ++c) m.put(r, c, f(scalar(r, c), b.scalar(r, c)));
         return m;
     }
 
@@ -290,7 +285,7 @@ inline double norm(const Mat& m) {
     const int cn = m.channels();
     for (int r = 0; r < m.rows; ++r)
         for (int c = 0; c < m.cols * cn; ++c) {
-            const double v = m.depth() == CV_64F ? m.ptr<double>(r)[c] : (double)m.ptr<float>(r)[c];
+            const double v = m.scalar(r, c);
             s += v * v;
         }
     return std::sqrt(s);

@@ -41,6 +41,11 @@
  *   mcc_omnirect_create ......... the maps of undistortImage (:543-544), built once and kept on the
  *                                 device for a stream of frames.
  *   mcc_omnirect_remap .......... its remap (:545) of one frame.
+ *   mcc_omnidir_stereo_reconstruct  cv::omnidir::stereoReconstruct (:1383-1539): rectify both images,
+ *                                 match them, the float disparity and the point cloud.
+ *   mcc_omnidir_sgbm ............ the StereoSGBM::create(...)->compute call in it (:1437-1439), restated.
+ *   mcc_omnirecon_create ........ its maps and every buffer, kept on the device for a stream of pairs.
+ *   mcc_omnirecon_compute ....... one frame pair through them.
  *
  * Parameters use the reference's encodeParameters layout (src/omnidir.cpp:1541-1568), CV_64F:
  *   x = [om_0(3), T_0(3), ..., om_{n-1}, T_{n-1}, fx, fy, s, cx, cy, xi, k1, k2, p1, p2], P = 6n + 10.
@@ -272,6 +277,85 @@ int mcc_omnirect_remap(mcc_omnirect *h, const unsigned char *src, long long src_
  * source (whatever the last remap left there); ms_per_frame = device time per launch from two HIP
  * events on the handle's stream. */
 int mcc_omnirect_time_remap(mcc_omnirect *h, int n_frames, double *ms_per_frame);
+
+/* ---------------------------------------------------------------- cv::omnidir::stereoReconstruct
+ * (src/omnidir.cpp:1383-1539): stereoRectify, undistortImage of both images with R1 / R2, a semi-global
+ * matcher on the rectified pair, the float disparity and the point cloud.
+ *
+ * The matcher restates StereoSGBM::create(0, numDisparities, SADWindowSize, 8 cn bs^2, 32 cn bs^2) in
+ * MODE_SGBM (one pass, five directions; disp12MaxDiff, preFilterCap, uniquenessRatio and the speckle
+ * filter at their zero defaults).  Its specification is DESIGN.md 7e and the numpy model
+ * tests/npsgbm.py; all of its arithmetic is integer.  Agreement with a real OpenCV build is NOT
+ * claimed bit for bit.  Its output is int16 [height][width], disparity x 16, -16 where there is none
+ * (always in the columns x < numDisparities).
+ *
+ * Refused with MCC_EINVAL before any device work: a null pointer; channels other than 1 or 3, or not
+ * the same in both images; images of different sizes; a stride shorter than a row; a flag other than
+ * MCC_OMNI_RECTIFY_PERSPECTIVE / _LONGLATI; numDisparities <= 0, not a multiple of 16 or above 256; a
+ * matched width <= numDisparities or above 65535; SADWindowSize even or < 1; 93 cn bs^2 > 32767 (the
+ * block cost would leave 16 bits); a cost volume 2 height (width - numDisparities) numDisparities
+ * above MCC_OMNI_SGBM_MAX_COST_BYTES (the handle holds three times that); a point type other than
+ * MCC_OMNI_XYZRGB / MCC_OMNI_XYZ; T = 0 or a baseline along z (as mcc_omnidir_stereo_rectify); a
+ * singular Knew. */
+#define MCC_OMNI_XYZRGB 1   /* cv::omnidir::XYZRGB: 6 floats per point, x y z r g b */
+#define MCC_OMNI_XYZ 2      /* cv::omnidir::XYZ: 3 floats per point                */
+#define MCC_OMNI_SGBM_MAX_COST_BYTES (1LL << 30)
+
+/* the matcher alone on an already rectified pair; disparity is short[height * width] */
+int mcc_omnidir_sgbm(const unsigned char *left, int width, int height, int channels, long long left_stride,
+                     const unsigned char *right, int width2, int height2, int channels2, long long right_stride,
+                     int num_disparities, int sad_window_size, int device, short *disparity);
+
+/* The per-frame case: both cameras' fixed-point maps, the images, the signal planes, the cost
+ * volumes and the cloud stay on the device; compute is two uploads, the kernels and the downloads.
+ * new_width == 0 is the reference's empty newSize: the rectified images take the source size and,
+ * because the reference's cloud loop runs over newSize, the cloud is empty. */
+typedef struct mcc_omnirecon mcc_omnirecon;
+
+typedef struct mcc_omnirecon_desc {
+    const double *K1, *D1;  /* [9], [4] or NULL                                   */
+    double xi1;
+    const double *K2, *D2;
+    double xi2;
+    const double *R, *T;    /* [9], [3]: the second camera's pose                 */
+    int flag;               /* MCC_OMNI_RECTIFY_PERSPECTIVE or _LONGLATI          */
+    int num_disparities, sad_window_size;
+    int src_width, src_height;
+    int channels;           /* 1 or 3                                             */
+    int new_width, new_height;
+    const double *Knew;     /* [9] or NULL (K1)                                   */
+    int point_type;         /* MCC_OMNI_XYZRGB or MCC_OMNI_XYZ                    */
+    int device;
+} mcc_omnirecon_desc;
+
+int mcc_omnirecon_create(mcc_omnirecon **out, const mcc_omnirecon_desc *desc);
+void mcc_omnirecon_destroy(mcc_omnirecon *h);
+
+/* One frame pair.  disparity: float[out_h * out_w] in pixels, -1 without a match, 0 where the first
+ * rectified image is black.  rec1 / rec2: the rectified images with their row strides.  cloud: room
+ * for capacity points of 3 (XYZ) or 6 (XYZRGB) floats, in the reference's order (columns, then rows);
+ * *n_points = the number of points.  If it exceeds capacity the call is MCC_EINVAL, the message names
+ * the count needed, *n_points holds it, and the cloud is not written at all (disparity and the
+ * rectified images are).  cloud may be NULL with capacity 0. */
+int mcc_omnirecon_compute(mcc_omnirecon *h, const unsigned char *image1, long long stride1,
+                          const unsigned char *image2, long long stride2, float *disparity, unsigned char *rec1,
+                          long long rec1_stride, unsigned char *rec2, long long rec2_stride, float *cloud,
+                          long long capacity, long long *n_points);
+
+/* measurement, as mcc_omnirect_time_remap: n_frames back-to-back computes (remap, matcher, cloud; no
+ * transfers) on resident random frames; ms_per_frame from two HIP events on the handle's stream. */
+int mcc_omnirecon_time(mcc_omnirecon *h, int n_frames, double *ms_per_frame);
+
+/* stereoReconstruct in one call: a handle used once.  Both images' sizes and channel counts are
+ * arguments so that a mismatch can be refused. */
+int mcc_omnidir_stereo_reconstruct(const unsigned char *image1, int width, int height, int channels,
+                                   long long stride1, const unsigned char *image2, int width2, int height2,
+                                   int channels2, long long stride2, const double *K1, const double *D1, double xi1,
+                                   const double *K2, const double *D2, double xi2, const double *R, const double *T,
+                                   int flag, int num_disparities, int sad_window_size, int new_width, int new_height,
+                                   const double *Knew, int point_type, int device, float *disparity,
+                                   unsigned char *rec1, long long rec1_stride, unsigned char *rec2,
+                                   long long rec2_stride, float *cloud, long long capacity, long long *n_points);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 /*
  * mcc_omnidir.hpp -- C++ mirror of cv::omnidir::calibrate, cv::omnidir::stereoCalibrate and the
  * rectification calls undistortPoints / initUndistortRectifyMap / undistortImage / stereoRectify
- * (all below) over the C ABI (mcc_omnidir.h).  calibrate has
+ * and stereoReconstruct (all below) over the C ABI (mcc_omnidir.h).  calibrate has
  * the same name, argument order and meaning as include/opencv2/ccalib/omnidir.hpp's
  *
  *   double calibrate(InputArrayOfArrays objectPoints, InputArrayOfArrays imagePoints, Size size,
@@ -20,10 +20,12 @@
 
 #include <algorithm>
 #include <array>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "mcc_cvmat.hpp"
 #include "mcc_multicalib.hpp"
 #include "mcc_omnidir.h"
 #include "mcc_pnp.hpp"
@@ -268,6 +270,77 @@ inline void stereoRectify(const std::vector<double>& R, const Vec3d& T, std::arr
     if (!Rp) throw std::invalid_argument("omnidir::stereoRectify: R must hold 9 values (3 x 3) or 3 (a rotation vector)");
     if (mcc_omnidir_stereo_rectify(Rp, T.data(), R1.data(), R2.data()) != MCC_OK)
         throw std::runtime_error(std::string("omnidir::stereoRectify: ") + mcc_last_error());
+}
+
+/*
+ * cv::omnidir::stereoReconstruct (src/omnidir.cpp:1383-1539) with the reference's argument order and
+ * defaults, on the project's cv::Mat (mcc_cvmat.hpp): 8-bit images of 1 or 3 channels in, the float
+ * disparity (CV_32F), both rectified images and the cloud (N x 1, CV_32FC3 for XYZ, CV_32FC(6) for
+ * XYZRGB) out.  R is 3 x 3 or a rotation vector, Knew may be empty (K1), an empty newSize keeps the
+ * source size and, as in the reference, gives an empty cloud.  The matcher is the project's own
+ * restatement of StereoSGBM (mcc_omnidir.h).  What the reference's CV_Assert lines check
+ * throws std::invalid_argument, everything the C ABI refuses std::runtime_error.
+ */
+enum { XYZRGB = MCC_OMNI_XYZRGB, XYZ = MCC_OMNI_XYZ };
+
+namespace detail {
+
+// every scalar of a CV_32F / CV_64F matrix in row-major order, as double; n of them or it throws
+inline std::vector<double> scalars(const cv::Mat& m, size_t n, const char* what) {
+    std::vector<double> v;
+    if (m.depth() == CV_32F || m.depth() == CV_64F)
+        for (int r = 0; r < m.rows; ++r)
+            for (int c = 0; c < m.cols * m.channels(); ++c) v.push_back(m.scalar(r, c));
+    if (v.size() != n)
+        throw std::invalid_argument(std::string("omnidir::stereoReconstruct: ") + what + " must hold " + std::to_string(n) +
+                                    " CV_32F / CV_64F values");
+    return v;
+}
+
+inline cv::Mat& no_array() {   // the reference's noArray(): an output nobody asked for
+    static thread_local cv::Mat none;
+    return none;
+}
+
+}  // namespace detail
+
+inline void stereoReconstruct(const cv::Mat& image1, const cv::Mat& image2, const cv::Mat& K1, const cv::Mat& D1, double xi1,
+                              const cv::Mat& K2, const cv::Mat& D2, double xi2, const cv::Mat& R, const cv::Mat& T, int flag,
+                              int numDisparities, int SADWindowSize, cv::Mat& disparity, cv::Mat& image1Rec,
+                              cv::Mat& image2Rec, Size newSize = Size(), const cv::Mat& Knew = cv::Mat(),
+                              cv::Mat& pointCloud = detail::no_array(), int pointType = XYZRGB, int device = 0) {
+    const char* who = "omnidir::stereoReconstruct";
+    const std::vector<double> k1 = detail::scalars(K1, 9, "K1"), k2 = detail::scalars(K2, 9, "K2");
+    const std::vector<double> d1 = detail::scalars(D1, 4, "D1"), d2 = detail::scalars(D2, 4, "D2");
+    const std::vector<double> t = detail::scalars(T, 3, "T");
+    const std::vector<double> rv = detail::scalars(R, R.total() * R.channels() == 3 ? 3 : 9, "R");
+    std::array<double, 9> Rb{};
+    const double* Rp = detail::rotation(rv, Rb, who);
+    std::vector<double> kn;
+    if (!Knew.empty()) kn = detail::scalars(Knew, 9, "Knew");
+    for (const cv::Mat* im : {&image1, &image2})
+        if (im->empty() || im->depth() != CV_8U || (im->channels() != 1 && im->channels() != 3))
+            throw std::invalid_argument(std::string(who) + ": the images must be CV_8UC1 or CV_8UC3 and not empty");
+    const bool keep = newSize.width <= 0 || newSize.height <= 0;   // Size::empty()
+    const int w = keep ? image1.cols : newSize.width, h = keep ? image1.rows : newSize.height;
+    const bool cloud = &pointCloud != &detail::no_array() && !keep;
+    disparity.create(h, w, CV_32F);
+    image1Rec.create(h, w, image1.type());
+    image2Rec.create(h, w, image1.type());
+    const int nf = pointType == XYZ ? 3 : 6;
+    std::vector<float> pts(cloud ? (size_t)w * h * nf : 0);
+    long long n = 0;
+    const int rc = mcc_omnidir_stereo_reconstruct(
+        image1.data, image1.cols, image1.rows, image1.channels(), (long long)image1.step(), image2.data, image2.cols,
+        image2.rows, image2.channels(), (long long)image2.step(), k1.data(), d1.data(), xi1, k2.data(), d2.data(), xi2, Rp,
+        t.data(), flag, numDisparities, SADWindowSize, keep ? 0 : w, keep ? 0 : h, kn.empty() ? nullptr : kn.data(),
+        pointType, device, disparity.ptr<float>(), image1Rec.data, (long long)image1Rec.step(), image2Rec.data,
+        (long long)image2Rec.step(), pts.empty() ? nullptr : pts.data(), cloud ? (long long)w * h : 0, &n);
+    if (rc != MCC_OK) throw std::runtime_error(std::string(who) + ": " + mcc_last_error());
+    if (&pointCloud != &detail::no_array()) {
+        pointCloud.create((int)n, 1, CV_32FC(nf));
+        if (n > 0) std::memcpy(pointCloud.data, pts.data(), sizeof(float) * (size_t)n * nf);
+    }
 }
 
 }  // namespace omnidir

@@ -66,6 +66,14 @@ class _OmniRectDesc(ctypes.Structure):
                 ("device", ctypes.c_int)]
 
 
+class _OmniReconDesc(ctypes.Structure):
+    _fields_ = [("K1", _f64p), ("D1", _f64p), ("xi1", ctypes.c_double), ("K2", _f64p), ("D2", _f64p),
+                ("xi2", ctypes.c_double), ("R", _f64p), ("T", _f64p), ("flag", ctypes.c_int),
+                ("num_disparities", ctypes.c_int), ("sad_window_size", ctypes.c_int), ("src_width", ctypes.c_int),
+                ("src_height", ctypes.c_int), ("channels", ctypes.c_int), ("new_width", ctypes.c_int),
+                ("new_height", ctypes.c_int), ("Knew", _f64p), ("point_type", ctypes.c_int), ("device", ctypes.c_int)]
+
+
 _LIB = None
 
 
@@ -190,11 +198,23 @@ def lib():
                 ("mcc_omnirect_create", [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_OmniRectDesc)]),
                 ("mcc_omnirect_destroy", [ctypes.c_void_p]),
                 ("mcc_omnirect_remap", [ctypes.c_void_p, _u8p, _ll, _u8p, _ll]),
-                ("mcc_omnirect_time_remap", [ctypes.c_void_p, ctypes.c_int, _f64p])):
+                ("mcc_omnirect_time_remap", [ctypes.c_void_p, ctypes.c_int, _f64p]),
+                ("mcc_omnidir_sgbm", [_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ll] * 2 + [ctypes.c_int] * 3 + [_i16p]),
+                ("mcc_omnirecon_create", [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_OmniReconDesc)]),
+                ("mcc_omnirecon_destroy", [ctypes.c_void_p]),
+                ("mcc_omnirecon_compute", [ctypes.c_void_p, _u8p, _ll, _u8p, _ll, _f32p, _u8p, _ll, _u8p, _ll, _f32p, _ll,
+                                           ctypes.POINTER(_ll)]),
+                ("mcc_omnirecon_time", [ctypes.c_void_p, ctypes.c_int, _f64p]),
+                ("mcc_omnidir_stereo_reconstruct", [_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ll] * 2 +
+                 [_f64p, _f64p, ctypes.c_double] * 2 + [_f64p, _f64p] + [ctypes.c_int] * 5 + [_f64p, ctypes.c_int,
+                                                                                             ctypes.c_int, _f32p, _u8p, _ll,
+                                                                                             _u8p, _ll, _f32p, _ll,
+                                                                                             ctypes.POINTER(_ll)])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
-        if hasattr(L, "mcc_omnirect_destroy"):
-            L.mcc_omnirect_destroy.restype = None
+        for name in ("mcc_omnirect_destroy", "mcc_omnirecon_destroy"):
+            if hasattr(L, name):
+                getattr(L, name).restype = None
         _LIB = L
     return _LIB
 
@@ -733,6 +753,7 @@ def omnidir_stereo_calibrate(off, obj, img1, img2, image_size1, image_size2, fla
 # initUndistortRectifyMap (:348-533), undistortImage (:538-546), stereoRectify (:2190-2227).
 RECTIFY_PERSPECTIVE, RECTIFY_CYLINDRICAL, RECTIFY_LONGLATI, RECTIFY_STEREOGRAPHIC = 1, 2, 3, 4
 MAP_FLOAT, MAP_FIXED = 1, 2
+XYZRGB, XYZ = 1, 2   # cv::omnidir's point types of stereoReconstruct
 
 
 def _mat3(a, what, vector_ok=False):
@@ -889,3 +910,94 @@ class OmniRectifier:
         ms = ctypes.c_double(0)
         _check(lib().mcc_omnirect_time_remap(self.h, int(n_frames), ctypes.byref(ms)), "mcc_omnirect_time_remap")
         return ms.value
+
+
+def omnidir_sgbm(left, right, num_disparities, sad_window_size, device=0):
+    """The semi-global matcher of stereoReconstruct alone (tests/npsgbm.py) on a rectified
+    uint8 pair of 1 or 3 channels: int16 [h, w], disparity x 16, -16 where there is none."""
+    left, w, h, c, ls = _image(left, "left")
+    right, w2, h2, c2, rs = _image(right, "right")
+    disp = np.zeros((max(h, 0), max(w, 0)), np.int16)
+    _check(lib().mcc_omnidir_sgbm(_ptr(left, _u8p), w, h, c, ls, _ptr(right, _u8p), w2, h2, c2, rs, int(num_disparities),
+                                  int(sad_window_size), device, _ptr(disp, _i16p)), "mcc_omnidir_sgbm")
+    return disp
+
+
+class OmniReconstructor:
+    """The per-frame case of stereoReconstruct (mcc_omnirecon): both cameras' fixed-point maps, the
+    images, the cost volumes and the cloud stay on the device for a stream of frame pairs.
+
+    new_size = (width, height), or None for the reference's empty newSize: the rectified images take
+    the source size and the cloud is empty, because the reference's cloud loop runs over newSize."""
+
+    def __init__(self, K1, D1, xi1, K2, D2, xi2, R, T, flag, num_disparities, sad_window_size, src_size, channels=1,
+                 new_size=None, Knew=None, point_type=XYZRGB, device=0):
+        self._keep = [_mat3(K1, "K1"), _vec(D1, 4, "D1"), _mat3(K2, "K2"), _vec(D2, 4, "D2"), _mat3(R, "R", True),
+                      _vec(T, 3, "T"), _mat3(Knew, "Knew")]
+        self.src_size = (int(src_size[0]), int(src_size[1]))
+        self.out_size = self.src_size if new_size is None else (int(new_size[0]), int(new_size[1]))
+        self.channels, self.point_type = int(channels), int(point_type)
+        d = _OmniReconDesc()
+        d.K1, d.D1, d.K2, d.D2, d.R, d.T, d.Knew = (_ptr(a, _f64p) for a in self._keep)
+        d.xi1, d.xi2, d.flag, d.device = float(xi1), float(xi2), int(flag), device
+        d.num_disparities, d.sad_window_size = int(num_disparities), int(sad_window_size)
+        d.src_width, d.src_height = self.src_size
+        d.new_width, d.new_height = (0, 0) if new_size is None else self.out_size
+        d.channels, d.point_type = self.channels, self.point_type
+        h = ctypes.c_void_p()
+        _check(lib().mcc_omnirecon_create(ctypes.byref(h), ctypes.byref(d)), "mcc_omnirecon_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcc_omnirecon_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def compute(self, image1, image2, capacity=None):
+        """One frame pair -> (disparity float32 [h, w], rec1, rec2, cloud float32 [n, 3 or 6]).  capacity
+        bounds the number of points (default: every pixel); too small a one raises MccError."""
+        image1, w1, h1, c1, s1 = _image(image1, "image1")
+        image2, w2, h2, c2, s2 = _image(image2, "image2")
+        if (w1, h1) != self.src_size or (w2, h2) != self.src_size or c1 != self.channels or c2 != self.channels:
+            raise MccError(f"both images must be {self.src_size[1]} x {self.src_size[0]} x {self.channels}")
+        w, h = self.out_size
+        nf = 3 if self.point_type == XYZ else 6
+        cap = w * h if capacity is None else int(capacity)
+        disp = np.zeros((h, w), np.float32)
+        rec1, rs1 = _dst_image(None, w, h, c1, image1.ndim == 2)
+        rec2, rs2 = _dst_image(None, w, h, c1, image1.ndim == 2)
+        cloud = np.zeros((max(cap, 0), nf), np.float32)
+        n = ctypes.c_longlong(0)
+        _check(lib().mcc_omnirecon_compute(self.h, _ptr(image1, _u8p), s1, _ptr(image2, _u8p), s2, _ptr(disp, _f32p),
+                                           _ptr(rec1, _u8p), rs1, _ptr(rec2, _u8p), rs2,
+                                           _ptr(cloud, _f32p) if cap > 0 else None, cap, ctypes.byref(n)),
+               "mcc_omnirecon_compute")
+        return disp, rec1, rec2, cloud[:n.value].copy()
+
+    def time(self, n_frames):
+        """Device milliseconds per frame pair over n_frames back-to-back computes on resident random frames."""
+        ms = ctypes.c_double(0)
+        _check(lib().mcc_omnirecon_time(self.h, int(n_frames), ctypes.byref(ms)), "mcc_omnirecon_time")
+        return ms.value
+
+
+def omnidir_stereo_reconstruct(image1, image2, K1, D1, xi1, K2, D2, xi2, R, T, flag, num_disparities, sad_window_size,
+                               new_size=None, Knew=None, point_type=XYZRGB, capacity=None, device=0):
+    """cv::omnidir::stereoReconstruct: (disparity, image1Rec, image2Rec, pointCloud).  R is a 3 x 3 matrix
+    or a rotation vector; new_size and capacity as OmniReconstructor."""
+    image1, w, h, c, _ = _image(image1, "image1")
+    image2, w2, h2, c2, _ = _image(image2, "image2")
+    if (w2, h2, c2) != (w, h, c):
+        raise MccError("the two images must have the same size and number of channels")
+    rec = OmniReconstructor(K1, D1, xi1, K2, D2, xi2, R, T, flag, num_disparities, sad_window_size, (w, h), c, new_size,
+                            Knew, point_type, device)
+    try:
+        return rec.compute(image1, image2, capacity)
+    finally:
+        rec.close()
