@@ -263,6 +263,51 @@ def two_level_pair(rng, H, W, d_left, d_right, split, cn=1):
     return np.ascontiguousarray(left.astype(np.uint8)), np.ascontiguousarray(right)
 
 
+# ------------------------------------------------------------------ a rig whose rectification is the identity
+# Two pinhole cameras (xi = 0, no distortion) side by side: R = I and T along -x give R1 = R2 = I, so with
+# Knew = K the rectified image is the source and every pixel of `real` can be set through the public entry.
+IDENT_F = 100.0
+IDENT_T = np.array([-0.3, 0.0, 0.0])      # bf = 0.3 * 100 = 30: a 20 px shift lies at depth 1.5
+IDENT_D = np.zeros(4)
+SEG_ROWS = 64                             # rows of one column segment of the device's cloud stage
+
+
+def ident_k(w, h, dx=0.0, dy=0.0):
+    """the identity rig's camera matrix for a w x h image: the principal point a quarter pixel off the
+    centre, moved by (dx, dy).  Off the pixel grid on purpose: in the column and the row of a principal
+    point that lies on a pixel the cloud's x or y is 0 in exact arithmetic, what comes out is the rounding
+    residue of Kinv00 * i + Kinv02 (0 or some 1e-17, depending on how the inverse was rounded), and a
+    distance in ulp between two such residues means nothing"""
+    return np.array([[IDENT_F, 0, w / 2 + 0.25 + dx], [0, IDENT_F, h / 2 + 0.25 + dy], [0, 0, 1]])
+
+
+def cloud_scene(kind, H, W, cn=1, seed=7):
+    """the pairs of tests/test_omnidir_cloud.py: a texture seen at 20 px (15 px for `threshold`, the
+    cloud's own bar), with parts of the left image black -- black left pixels have real = 0"""
+    left, right = shifted_pair(np.random.default_rng(seed), H, W, 15 if kind == "threshold" else 20, cn)
+    if kind == "black":
+        left[:] = 0
+    elif kind == "bands":          # every other band of five columns, and the whole second segment of rows
+        left[:, (np.arange(W) // 5) % 2 == 1] = 0
+        left[SEG_ROWS:2 * SEG_ROWS] = 0
+    elif kind == "tail":           # three pixels at the very end of the cloud's order
+        keep = left[H - 1, W - 3:].copy()
+        left[:] = 0
+        left[H - 1, W - 3:] = keep
+    else:
+        assert kind in ("dense", "threshold"), kind
+    return left, right
+
+
+def slot_counts(real, new_size):
+    """int [w, n_seg]: points per column and segment of SEG_ROWS rows, in the order the device scans them"""
+    w, h = new_size
+    n_seg = (h + SEG_ROWS - 1) // SEG_ROWS
+    pts = np.zeros((n_seg * SEG_ROWS, w), np.int64)
+    pts[:h] = real[:h, :w] > 15
+    return pts.reshape(n_seg, SEG_ROWS, w).sum(1).T
+
+
 # ------------------------------------------------------------------ a rendered stereo pair
 # the two Mei cameras of test_rectified_stereo_pair_rows_agree at 160 x 120
 RIG_SIZE = (160, 120)
