@@ -445,7 +445,7 @@ __device__ __forceinline__ void fold_chunk(const LinArgs& la, int c) {
 // the status says there is one), then kFoldEmpty back into all of them, and k_schur's one-level finish
 // (sums in item order, placement, the refinement or elimination, the camera update)
 template <int U>
-__device__ __forceinline__ void fold_final_u(const LinArgs& la) {
+__device__ __forceinline__ void fold_final_u(const LinArgs& la, const SolvePre* pre) {
     const SchurArgs& a = la.fsa;
     State* st = a.state;
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -520,7 +520,7 @@ __device__ __forceinline__ void fold_final_u(const LinArgs& la) {
     __syncthreads();
     SSTAMP(srow, 8, 0);   // the partials landed in LDS
     // (the inverse only with this launch's tag: fold_final_direct)
-    schur_finish(a, np, iter, cn0, cn1, err_now, useiv && s_status == (double)(iter + 1), srow);
+    schur_finish(a, np, iter, cn0, cn1, err_now, useiv && s_status == (double)(iter + 1), srow, pre);
 }
 // The final workgroup with the sums formed where the words land (LinArgs::fold_direct: 512 threads,
 // <= 8 items per camera-pair block, <= 4 norm chunks -- config4): thread t < 48 nblk owns entry t of
@@ -536,7 +536,7 @@ __device__ __forceinline__ void fold_final_reset(const LinArgs& la, const double
         if ((have >> q) & 1) fold_empty(const_cast<double*>(src[q]));
     if (threadIdx.x == 0 && useiv) fold_empty(la.fiv + la.fsa.m * la.fsa.m);
 }
-__device__ __forceinline__ void fold_final_direct(const LinArgs& la) {
+__device__ __forceinline__ void fold_final_direct(const LinArgs& la, const SolvePre* pre) {
     const SchurArgs& a = la.fsa;
     State* st = a.state;
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -711,24 +711,44 @@ __device__ __forceinline__ void fold_final_direct(const LinArgs& la) {
     SSTAMP(srow, 3, 0);
     SolveCtx sc = a.solve;
     sc.stamps = srow;
-    solve_global<false>(sc, S, r, norms[0], norms[1], nullptr, ivok ? Iv : nullptr);
+    solve_global<false>(sc, S, r, norms[0], norms[1], nullptr, ivok ? Iv : nullptr, pre);
     SSTAMP(srow, 7, 0);
     // every word back to kFoldEmpty for the next launch's producers (after the solve: ahead of it these
-    // 4 000 write-through stores held up the placement's)
+    // 4 000 write-through stores held up the placement's; waves 2..7 issuing theirs under the refinement
+    // gained nothing at config4, profiles/fold_step_end)
     fold_final_reset(la, src, have, useiv);
+    SSTAMP_DRAINED(srow, 15, 0);   // MCC_DIAG: thread 0's wave has its stores, the resets last, completed
 }
+// MCC_FOLD_EARLY=0 (A/B and diagnostic builds): the final workgroup fetches nothing for the solve ahead of
+// its poll (fold_final); the solve then loads its state, step factor and parameters itself, after the sums
+#ifndef MCC_FOLD_EARLY
+#define MCC_FOLD_EARLY 1
+#endif
 // (one batch width per k_group shape: the host keeps 48 parts + m^2 + 1 within k_schur's one-level
 // bound, kSchurOneLevelLoads x 256 words)
 template <int NT>
 __device__ __forceinline__ void fold_final(const LinArgs& la) {
+    // The final workgroup spins until the last group's words have landed (~20 us at config4), and what
+    // the solve needs besides the sums is known at its entry: the state words, the step factor and the
+    // camera parameters come in now, so that the stop test between the placed sums and the camera update
+    // is arithmetic on LDS words instead of two dependent round trips (or a pow past the table).
+    __shared__ SolvePre s_pre;
+    // (never null here, so that the solve keeps no second copy of the loads and the pow; without
+    // fuse_solve there is no solve to read it)
+    const SolvePre* pre = MCC_FOLD_EARLY ? &s_pre : nullptr;
+    if (MCC_FOLD_EARLY && la.fsa.fuse_solve) {
+        SolveCtx sc = la.fsa.solve;
+        sc.stamps = la.fsa.stamps ? la.fsa.stamps + kSchurStampStride * (size_t)la.fold_parts : nullptr;   // MCC_DIAG
+        solve_prefetch(sc, &s_pre);   // (visible to the solve's threads through the poll's barriers)
+    }
     if (NT == 512 && la.fold_direct) {
-        fold_final_direct(la);
+        fold_final_direct(la, pre);
         return;
     }
     constexpr int UM = kSchurOneLevelLoads * 256 / NT;
     const int n = 48 * la.fold_parts + (la.fsa.ssinv != nullptr ? la.fsa.m * la.fsa.m + 1 : 0);
-    if (n <= UM / 2 * NT) fold_final_u<UM / 2>(la);
-    else fold_final_u<UM>(la);
+    if (n <= UM / 2 * NT) fold_final_u<UM / 2>(la, pre);
+    else fold_final_u<UM>(la, pre);
 }
 
 #ifndef MCC_GROUP_PAIR_THREADS

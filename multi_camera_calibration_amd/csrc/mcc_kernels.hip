@@ -84,6 +84,21 @@ namespace mcc {
 #else
 #define SSTAMP(ptr, k, who) do { } while (0)
 #endif
+// the same after a wait of the stamping wave (the diagnostic build only: the wait is not in the product):
+// "vmcnt(0) lgkmcnt(0)" once its loads and stores in flight have completed, "lgkmcnt(0)" its scalar loads
+#ifdef MCC_DIAG
+#define SSTAMP_AFTER(ptr, k, who, counters)                                                        \
+    do {                                                                                           \
+        if (threadIdx.x == (who) && (ptr)) {                                                       \
+            asm volatile("s_waitcnt " counters ::: "memory");                                      \
+            (ptr)[k] = (long long)MCC_DIAG_CLOCK();                                                \
+            __builtin_amdgcn_sched_barrier(0);                                                     \
+        }                                                                                          \
+    } while (0)
+#else
+#define SSTAMP_AFTER(ptr, k, who, counters) do { } while (0)
+#endif
+#define SSTAMP_DRAINED(ptr, k, who) SSTAMP_AFTER(ptr, k, who, "vmcnt(0) lgkmcnt(0)")
 // the clock into a variable of the calling wave (every wave stamps; k_group's per-wave round-0 stamps)
 #ifdef MCC_DIAG
 #define WSTAMP(v)                                                                                  \
@@ -964,9 +979,30 @@ __device__ __forceinline__ double photo_flag_norm(int err, int w, double v) {
     return w == 1 && (err & kErrPhotoNotPD) ? __builtin_nan("") : v;
 }
 
+// What solve_global's stop test and camera update take besides the step's sums: the state words, the
+// step factor alpha (a load that depends on the iteration's, or a pow() of ~200 instructions past the
+// table) and the global-block parameters.  None of it depends on the sums or changes during the
+// launch, so a caller that waits for the sums (k_group's folded final workgroup, fold_final) fetches it
+// ahead of its wait (solve_prefetch) and hands it in; the other callers pass none and solve_global
+// fetches it itself, beside wave 1's elimination.
+// The error word may be read that early: bit 0 (a photo block of THIS launch that is not positive
+// definite) reaches the final workgroup through the norm slot (the chunks' not-PD counts,
+// photo_flag_norm), not through this word, and bit 1 is set only by the solving workgroup itself, after
+// the read either way; any bit an earlier launch left has set `done`, and the launch does nothing.
+struct SolveState {
+    int err0, iter, crit_type, max_count;
+    double eps, alpha;
+};
+struct SolvePre {      // (LDS)
+    SolveState st;     // thread 0's
+    float x[32];       // the global block, m <= 30
+};
+__device__ __forceinline__ void solve_prefetch(const SolveCtx& a, SolvePre* q);
+
 template <bool LARGE>
 __device__ __forceinline__ void solve_global(const SolveCtx& a, double* S, double* r, double normG2, double normX2,
-                                             const WarmCtx* warm = nullptr, const double* Iv = nullptr);
+                                             const WarmCtx* warm = nullptr, const double* Iv = nullptr,
+                                             const SolvePre* pre = nullptr);
 
 __device__ __forceinline__ unsigned ld_agent_u32(const unsigned* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3400,11 +3436,12 @@ __global__ __launch_bounds__(kSolveThreads) void k_sinv_helper(WarmCtx w, int m,
         if (w.refine) {
             // [S | r] staged, x = S^-1 r refined with the held inverse of system e - 1, published.
             // k_schur publishes e when it STARTS (round 6; it used to after its second hand-off level), and
-            // every word of prev2 is its own flag (kFoldEmpty until its block's sc1 store lands; the helper
-            // empties the buffer again once it has refined), so the staging polls the words as the blocks
-            // land instead of starting after the last one: 5 x 16-byte loads per thread (the landed ones
-            // re-read at the buffer's first word), a short sleep between passes.  The pad word of an odd
-            // packed length is 0 for good (mcc_create).  (n2 <= 2 093 at m = 90: one batch of 512 x 5)
+            // every word of prev2 is its own flag (kFoldEmpty until its block's sc1 store lands; the next
+            // step's k_schur empties them again, schur_block_store, not the helper), so the staging polls
+            // the words as the blocks land instead of starting after the last one: 5 x 16-byte loads per
+            // thread (the landed ones re-read at the buffer's first word), a short sleep between passes.
+            // The pad word of an odd packed length is 0 for good (mcc_create).  (n2 <= 2 093 at m = 90:
+            // one batch of 512 x 5)
             if (!w.poll) {   // (published complete: round 5's one batch -- the polling loop below cost the
                              // 8-rank shard, whose step the helper's cycle bounds, 0.9 us even in one pass)
                 for (int q0 = 0; q0 < n2; q0 += 5 * (int)blockDim.x) {
@@ -3744,10 +3781,38 @@ __device__ __forceinline__ bool small_refine(const double* S, double* r, const d
     }
 }
 
+// the step factor of iteration k: the host's table (src/multicalib.cpp:483), past its end the same power
+// on the device
+__device__ __forceinline__ double solve_alpha(const SolveCtx& a, int k) {
+    return a.do_update ? (k < a.n_alpha ? a.alpha[k] : pow(0.95, (double)k + 1.0)) : 0.0;
+}
+// ahead of the caller's wait for the sums: thread 0 the state words and the step factor, threads 128..
+// the global-block parameters (solve_global's own threads for them), into the caller's LDS
+// (MCC_DIAG: stamped once the state words are in, and once alpha is)
+__device__ __forceinline__ void solve_prefetch(const SolveCtx& a, SolvePre* q) {
+    State* st = a.state;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        SolveState v;
+        v.err0 = __hip_atomic_load(&st->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v.iter = st->iter;
+        v.crit_type = st->crit_type;
+        v.max_count = st->max_count;
+        v.eps = st->eps;
+        SSTAMP_DRAINED(a.stamps, 11, 0);
+        v.alpha = solve_alpha(a, v.iter);
+        SSTAMP_AFTER(a.stamps, 12, 0, "lgkmcnt(0)");
+        q->st = v;
+    } else if (tid >= 128 && tid < 128 + a.m) {
+        q->x[tid - 128] = a.x[tid - 128];
+    }
+}
+
 // LARGE: m > 30 (k_solve only: the register-tiled elimination needs the whole workgroup's registers)
+// pre: the caller's prefetch (solve_prefetch) or null
 template <bool LARGE>
 __device__ __forceinline__ void solve_global(const SolveCtx& a, double* S, double* r, double normG2, double normX2,
-                                             const WarmCtx* warm, const double* Iv) {
+                                             const WarmCtx* warm, const double* Iv, const SolvePre* pre) {
     State* st = a.state;
     const int m = a.m, tid = threadIdx.x;
     __shared__ int stop, s_iter;
@@ -3762,32 +3827,40 @@ __device__ __forceinline__ void solve_global(const SolveCtx& a, double* S, doubl
     WarmStage ws;
     if (wrm && !warm->refine) warm_issue(S, m, ws);
     if (wrm && tid == 64) warm_check(*warm, &s_use, &s_ep);
+    const float* xs = pre ? pre->x : s_x;
     if (tid == 0) {
-        // the error bits the step's photo work set (bit 0), read with the state so that the stop
+        // the state words and the step factor: the caller's (fetched ahead of its wait for the sums, which
+        // leaves the stop test's arithmetic and the state's stores here) or loaded now.
+        // The error bits the step's photo work set (bit 0) are read with the state so that the stop
         // at the end needs no further round trip.  On a sharded problem a photo block that is not
         // positive definite on ANY rank arrives here as a NaN in the summed normX2 slot
         // (photo_flag_norm): every rank then stops on the same step with the same error
-        s_err0 = __hip_atomic_load(&st->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_err0 = pre ? pre->st.err0 : __hip_atomic_load(&st->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (!(normX2 == normX2)) s_err0 |= kErrPhotoNotPD;
         s_bad = 0;
-        const int k = st->iter;
+        const int k = pre ? pre->st.iter : st->iter;
+        if (!pre) SSTAMP_DRAINED(a.stamps, 11, 0);   // MCC_DIAG: the error word and the iteration are in
         double change = 1.0;
         if (k > 0) {
             change = sqrt(normG2) / sqrt(normX2);   // change = norm(G) / norm(x) (:504)
             st->change = change;
         }
-        const int ty = st->crit_type;
-        int s = (ty == 1 && k >= st->max_count) || (ty == 2 && change <= st->eps) ||
-                (ty == 3 && (change <= st->eps || k >= st->max_count));
+        const int ty = pre ? pre->st.crit_type : st->crit_type;
+        const auto max_count = [&] { return pre ? pre->st.max_count : st->max_count; };
+        const auto eps = [&] { return pre ? pre->st.eps : st->eps; };
+        int s = (ty == 1 && k >= max_count()) || (ty == 2 && change <= eps()) ||
+                (ty == 3 && (change <= eps() || k >= max_count()));
         if (!a.do_update) s = 0;
         stop = s;
         if (s) st->done = 1;
         st->pending = 0;   // this step's k_linearize has applied the previous update
-        const double alpha = a.do_update ? (k < a.n_alpha ? a.alpha[k] : pow(0.95, (double)k + 1.0)) : 0.0;
+        const double alpha = pre ? pre->st.alpha : solve_alpha(a, k);
+        if (!pre) SSTAMP_AFTER(a.stamps, 12, 0, "lgkmcnt(0)");   // MCC_DIAG: the criteria and alpha are in
         st->alpha = alpha;
         s_alpha = alpha;
         s_iter = k;
-    } else if (tid >= 128 && tid < 128 + m) {
+        SSTAMP(a.stamps, 13, 0);   // wave 0 at the barrier
+    } else if (!pre && tid >= 128 && tid < 128 + m) {
         s_x[tid - 128] = a.x[tid - 128];   // global-block parameters, fetched while wave 1 eliminates
     } else if (!LARGE && tid >= 64 && tid < 128) {
         // speculative: the elimination does not depend on the stop test (its result is unused
@@ -3836,7 +3909,7 @@ __device__ __forceinline__ void solve_global(const SolveCtx& a, double* S, doubl
             a.delta[i] = d;
             if (a.do_update) {
                 const float G = (float)(alpha * d);   // G = alpha*delta -> CV_32F (:491-496)
-                const float xn = s_x[i] + G;          // x = x + G (:501)
+                const float xn = xs[i] + G;           // x = x + G (:501)
                 a.x[i] = xn;
                 g2 += (double)G * (double)G;
                 x2 += (double)xn * (double)xn;
@@ -3931,7 +4004,7 @@ constexpr int kMaxItemsPerBlock = 24;   // host splits each block's pairs into <
 // on its loads, costs a round trip per load or iteration: 5 us at config4 in the first form), and
 // the sums are formed from LDS.
 __device__ __forceinline__ void schur_finish(const SchurArgs& a, int nparts, int iter, double cn0, double cn1,
-                                             int err_now, bool iv, long long* srow);
+                                             int err_now, bool iv, long long* srow, const SolvePre* pre = nullptr);
 __device__ __forceinline__ void schur_one_level(const SchurArgs& a, int iter_e) {
     State* st = a.state;
     const int tid = threadIdx.x;
@@ -3992,8 +4065,9 @@ __device__ __forceinline__ void schur_one_level(const SchurArgs& a, int iter_e) 
 // chunk, nparts of them) in itm, the block ranges in sbi, the inverse (iv) after S and r -- k_schur's
 // last arriver (schur_one_level) and k_group's folded final workgroup (fold_final) both land them there
 // srow: this workgroup's MCC_DIAG stamp row (k_schur's by grid index, the folded final's after the items)
+// pre: what the folded final workgroup fetched for the solve ahead of its poll (solve_prefetch), or null
 __device__ __forceinline__ void schur_finish(const SchurArgs& a, int nparts, int iter, double cn0, double cn1,
-                                             int err_now, bool iv, long long* srow) {
+                                             int err_now, bool iv, long long* srow, const SolvePre* pre) {
     State* st = a.state;
     const int tid = threadIdx.x;
     const int m = a.m, nb = m / 6, ntri = m * (m + 1) / 2;
@@ -4098,7 +4172,7 @@ __device__ __forceinline__ void schur_finish(const SchurArgs& a, int nparts, int
     SSTAMP(srow, 3, 0);
     SolveCtx sc = a.solve;
     sc.stamps = srow;   // slots 4..6 of this row
-    solve_global<false>(sc, S, r, norms[0], norms[1], nullptr, Iv);
+    solve_global<false>(sc, S, r, norms[0], norms[1], nullptr, Iv, pre);
     SSTAMP(srow, 7, 0);
 }
 #ifndef MCC_SCHUR_LOADS

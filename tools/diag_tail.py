@@ -7,6 +7,12 @@ Never quote this build's run time.
 
     MCC_LIB=multi_camera_calibration_amd/libmcc_diagrt.so python tools/diag_tail.py config3 [shard N] [reps]
 With a shard N the problem is rank 0's photo shard of config3 split N ways (bench.py shard_line).
+
+On a folded step (config4: one k_group launch) it prints the final workgroup's timeline instead
+(fold_timeline): its entry, the solve's prefetch, the landed words, the placed sums, both waves of the
+solve, the camera update and the drain of the hand-off words' resets.  TAIL_RAMP=<steps> (default 40) sets
+the free-running steps before the stamped ones: 40 leaves the iteration inside the step-factor table (a
+real optimisation's regime), 10000 past its end (bench.py's timed region, the pow branch).
 """
 import os
 import sys
@@ -30,8 +36,53 @@ ba = api.BundleAdjuster(p)
 print(f"{cfg} shard 1/{shard}: {p.n_photos} views, {p.n_edges} edges, path {ba.step_kernels()}, "
       f"{ba.photo_groups()} groups", flush=True)
 ba.set_params(p.x0)
-ba.step(40)
+ba.step(int(os.environ.get("TAIL_RAMP", "40")))
 ba.synchronize()
+
+
+def fold_timeline():
+    """The folded step's final workgroup (its stamp row follows the items' and norm chunks'; slots as
+    stamped in fold_final_direct / fold_final_u, schur_finish and solve_global), us from the first
+    group's start.  Slots 11 and 12 are stamped once the loads before them have completed, 15 once wave 0's
+    stores have (s_waitcnt, in the diagnostic build only)."""
+    names = [(10, "final workgroup's entry"), (11, "state words in (thread 0)"), (12, "alpha in (thread 0)"),
+             (8, "every word landed"), (9, "sums placed"), (0, "solve entry"),
+             (13, "wave 0 at the solve's barrier"), (2, "wave 1: refinement / elimination end"),
+             (4, "stop test passed (all waves)"), (6, "camera update stored"), (7, "solve's end"),
+             (15, "wave 0: stores drained (resets last)")]
+    ba.stamps()   # arm
+    nv = max(p.n_photos, 1)
+    rows = []
+    for _ in range(reps):
+        ba.step(1)
+        ba.synchronize()
+        raw = ba.stamps().reshape(-1).astype(np.int64)
+        ph = raw[:32 * nv].reshape(nv, 32)
+        g0, ge = ph[:, 0][ph[:, 0] > 0], ph[:, 10][ph[:, 10] > 0]
+        sch = raw[32 * nv:32 * nv + 16 * 4096].reshape(-1, 16)
+        fin = sch[(sch[:, 10] > 0) & (sch[:, 9] > 0)]
+        if not len(g0) or len(fin) != 1:
+            continue
+        t0 = g0.min()
+        items = sch[(sch[:, 0] >= t0) & (sch[:, 10] == 0)]
+        row = {"last group ends": (ge.max() - t0) * 0.01, "items and chunks summed": (items[:, 1].max() - t0) * 0.01}
+        for k, n in names:
+            row[n] = (fin[0, k] - t0) * 0.01 if fin[0, k] > 0 else float("nan")
+        rows.append(row)
+    print(f"iteration {int(os.environ.get('TAIL_RAMP', '40'))}+, median over {len(rows)} steps (us from the first group's start):")
+    for k in rows[0]:
+        v = np.array([r[k] for r in rows])
+        print(f"  {k:>38s} {np.nanmedian(v):8.2f}   (min {np.nanmin(v):7.2f}, max {np.nanmax(v):7.2f})")
+    for a, b in (("sums placed", "camera update stored"), ("sums placed", "wave 0 at the solve's barrier"),
+                 ("sums placed", "wave 1: refinement / elimination end"), ("camera update stored", "solve's end"),
+                 ("solve's end", "wave 0: stores drained (resets last)")):
+        print(f"  {a} -> {b}: {np.nanmedian([r[b] - r[a] for r in rows]):.2f} us")
+
+
+if ba.folded():
+    fold_timeline()
+    ba.close()
+    sys.exit(0)
 steps_per_rep = int(os.environ.get("TAIL_STEPS", "1"))   # > 1: the last of a batch (a resident helper's steady state)
 ba.stamps()   # arm
 nv = max(p.n_photos, 1)
