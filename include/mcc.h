@@ -249,6 +249,38 @@ int mcc_problem_stats(const mcc_problem *p, long long *corners, long long *edges
  * in rare cases a float32 ulp of the state) depend on the device model; MCC_FUSED pins it. */
 int mcc_problem_path(const mcc_problem *p, int *split_step, int *photo_groups);
 
+/* ---- pose seeding: cv::solvePnP (SOLVEPNP_ITERATIVE) as host/pnp.cpp restates it, for a whole batch
+ * of corner views in one launch (one wavefront per view, the Levenberg-Marquardt loop on the device).
+ * The sequence and the LM policy are mcc::pnp::solvePnP's (include/mcc_pnp.hpp); the Jacobian is
+ * analytic where the host takes central differences, so the two agree at the minimum, not bit for bit.
+ * A view's result depends on that view only, never on the rest of the batch.  Pinhole model of
+ * cv::projectPoints with D = k1 k2 p1 p2 [k3 [k4 k5 k6 [s1 s2 s3 s4]]]: nd is 0, 4, 5, 8 or 12.  At
+ * most 1024 corners per view. */
+typedef struct mcc_pnp_desc {
+    int n_views;
+    const int *view_off;     /* [n_views+1] corner offsets                          */
+    const double *obj;       /* [3*corners] object points                           */
+    const double *img;       /* [2*corners] observed corners (pixels)               */
+    const int *view_cam;     /* [n_views] camera of each view, or NULL (camera 0)   */
+    int n_cams;
+    const double *K;         /* [9*n_cams] camera matrices (row-major)              */
+    const double *D;         /* [nd*n_cams] distortion (may be NULL when nd is 0)   */
+    int nd;
+    int max_iter;            /* LM iterations at most (the host's is 50); 0 = return the closed-form initial pose */
+    int device;
+} mcc_pnp_desc;
+
+#define MCC_PNP_SOLVED 0       /* rvec, tvec and rms (pixels) are set                               */
+#define MCC_PNP_TOO_FEW 1      /* fewer than 4 points, or fewer than 6 off a plane: rms is -1       */
+#define MCC_PNP_DEGENERATE 2   /* collinear points, a rank-deficient homography or a non-finite result: rms is -1 */
+
+/* rvec[3*n_views], tvec[3*n_views], rms[n_views], status[n_views] (MCC_PNP_*); a view that is not
+ * solved gets a zero pose and never fails the batch.  MCC_EINVAL, before any device work, for a null
+ * pointer, n_views <= 0, a view_off that decreases, an nd outside the set, a view_cam out of range or
+ * a view of more than 1024 corners.  device_ms (may be NULL): the launch alone, by HIP events. */
+int mcc_solve_pnp_batch(const mcc_pnp_desc *d, double *rvec, double *tvec, double *rms, int *status,
+                        double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif

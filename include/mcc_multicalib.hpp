@@ -615,6 +615,10 @@ public:
     std::set<int> setOfTimestampIsMulticamera;
     std::vector<std::vector<bool>> timestampIsMulticamera;
     int invalidPoseCount = 0;   // views whose solvePnP translation failed isValidPose (dropped)
+    // opt-in: loadImages reads all of a run's corner files first and solves their poses in one GPU
+    // launch (mcc::pnp::solvePnPBatch) instead of one solvePnP per view on the host; the default does
+    // no device work.  DoubleSideCalibration inherits it.
+    bool gpuPnP = false;
     std::array<double, 16> doubleSideTransform{};   // CV_64F 4x4; all zero = not loaded
 
 protected:

@@ -74,6 +74,14 @@ class _OmniReconDesc(ctypes.Structure):
                 ("new_height", ctypes.c_int), ("Knew", _f64p), ("point_type", ctypes.c_int), ("device", ctypes.c_int)]
 
 
+class _PnpDesc(ctypes.Structure):
+    _fields_ = [("n_views", ctypes.c_int), ("view_off", _i32p), ("obj", _f64p), ("img", _f64p), ("view_cam", _i32p),
+                ("n_cams", ctypes.c_int), ("K", _f64p), ("D", _f64p), ("nd", ctypes.c_int), ("max_iter", ctypes.c_int),
+                ("device", ctypes.c_int)]
+
+
+PNP_SOLVED, PNP_TOO_FEW, PNP_DEGENERATE = 0, 1, 2
+
 _LIB = None
 
 
@@ -209,7 +217,8 @@ def lib():
                  [_f64p, _f64p, ctypes.c_double] * 2 + [_f64p, _f64p] + [ctypes.c_int] * 5 + [_f64p, ctypes.c_int,
                                                                                              ctypes.c_int, _f32p, _u8p, _ll,
                                                                                              _u8p, _ll, _f32p, _ll,
-                                                                                             ctypes.POINTER(_ll)])):
+                                                                                             ctypes.POINTER(_ll)]),
+                ("mcc_solve_pnp_batch", [ctypes.POINTER(_PnpDesc), _f64p, _f64p, _f64p, _i32p, _f64p])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
         for name in ("mcc_omnirect_destroy", "mcc_omnirecon_destroy"):
@@ -249,6 +258,41 @@ def _check(rc, what):
 
 def _ptr(a, t):
     return a.ctypes.data_as(t) if a is not None else None
+
+
+def solve_pnp(obj, img, off, K, D, view_cam=None, max_iter=50, device=0, return_ms=False):
+    """cv::solvePnP (SOLVEPNP_ITERATIVE, as host/pnp.cpp restates it) for a batch of views in one GPU
+    launch (mcc_solve_pnp_batch): the pose seeds x0 that optimizeExtrinsics starts from.
+
+    View v owns corners off[v]:off[v + 1] of obj [corners, 3] and img [corners, 2] (pixels) and is seen by
+    camera view_cam[v] (camera 0 without view_cam) of K [n_cams, 3, 3] (or one 3 x 3) and D [n_cams, nd]
+    (or one vector, or None), nd in {0, 4, 5, 8, 12}.  Returns (rvec [V, 3], tvec [V, 3], rms [V],
+    status [V]): status PNP_SOLVED, PNP_TOO_FEW (rms -1) or PNP_DEGENERATE (rms -1); a view's result
+    does not depend on the rest of the batch.  max_iter = 0 returns the closed-form initial poses.  With
+    return_ms the launch's device milliseconds are appended."""
+    off = np.ascontiguousarray(off, np.int32).reshape(-1)
+    obj = np.ascontiguousarray(obj, np.float64).reshape(-1, 3)
+    img = np.ascontiguousarray(img, np.float64).reshape(-1, 2)
+    K = np.ascontiguousarray(K, np.float64).reshape(-1, 3, 3)
+    n_cams = K.shape[0]
+    D = np.zeros((n_cams, 0)) if D is None else np.ascontiguousarray(D, np.float64).reshape(n_cams, -1)
+    n_views = len(off) - 1
+    if n_views >= 1 and (len(obj) < off[-1] or len(img) < off[-1]):
+        raise MccError(f"solve_pnp: off names {off[-1]} corners, obj has {len(obj)} and img {len(img)}")
+    cam = None
+    if view_cam is not None:
+        cam = np.ascontiguousarray(view_cam, np.int32).reshape(-1)
+        if len(cam) != n_views:
+            raise MccError(f"solve_pnp: view_cam has {len(cam)} entries for {n_views} views")
+    nv = max(n_views, 1)
+    rvec, tvec = np.zeros((nv, 3)), np.zeros((nv, 3))
+    rms, status, ms = np.zeros(nv), np.zeros(nv, np.int32), np.zeros(1)
+    d = _PnpDesc(n_views, _ptr(off, _i32p), _ptr(obj, _f64p), _ptr(img, _f64p), _ptr(cam, _i32p), n_cams,
+                 _ptr(K, _f64p), _ptr(D, _f64p) if D.shape[1] else None, D.shape[1], int(max_iter), int(device))
+    _check(lib().mcc_solve_pnp_batch(ctypes.byref(d), _ptr(rvec, _f64p), _ptr(tvec, _f64p), _ptr(rms, _f64p),
+                                     _ptr(status, _i32p), _ptr(ms, _f64p)), "mcc_solve_pnp_batch")
+    out = (rvec, tvec, rms, status)
+    return out + (float(ms[0]),) if return_ms else out
 
 
 def partition_photos(prob, nranks):

@@ -361,6 +361,50 @@ void MyMultiCameraCalibration::loadImages(const std::set<std::string>& outliers)
     namespace fsys = std::filesystem;
     if (!outliers.empty()) m_outliers = outliers;
     const int backN = _BackPatternSize.width * _BackPatternSize.height;
+    // one corner file as read (readTimestamps, readCorners): object points through float32
+    struct CornerView {
+        int cam = 0, timestamp = 0, n = 0;
+        std::string file;
+        std::vector<double> img, obj;
+    };
+    auto read_view = [](int cam, const std::string& file) {
+        CornerView v;
+        v.cam = cam;
+        v.file = file;
+        v.timestamp = std::stoi(fsys::path(file).stem().string());   // readTimestamps
+        stg::FileStorage fs(file, stg::FileStorage::READ);             // readCorners
+        if (!fs.isOpened()) throw std::runtime_error("cannot read " + file);
+        v.img = points_of(fs["corners"], 2, file, "corners");
+        const std::vector<double> objd = points_of(fs["objects"], 3, file, "objects");
+        v.n = (int)v.img.size() / 2;
+        if ((int)objd.size() != 3 * v.n) throw std::runtime_error(file + ": corners and objects differ in count");
+        v.obj.resize(objd.size());   // objectPoints.convertTo(CV_32F)
+        for (size_t k = 0; k < objd.size(); ++k) v.obj[k] = (double)(float)objd[k];
+        return v;
+    };
+    // what follows a view's solvePnP: the float cast, isValidPose, storeReaded
+    auto store_view = [&](const CornerView& v, const double r[3], const double t[3]) {
+        const std::array<float, 3> om{(float)r[0], (float)r[1], (float)r[2]};
+        const std::array<float, 3> tv{(float)t[0], (float)t[1], (float)t[2]};
+        if (!is_valid_pose(tv.data())) {   // the reference asserts (src/mymulticalib.cpp:210, :297)
+            if (strictReference) strict_abort("isValidPose(tvec)", "src/mymulticalib.cpp:210 (calcPatternPose)");
+            ++invalidPoseCount;
+            std::cout << "invalid pattern :" << invalidPoseCount << ", " << v.file << std::endl;
+            return;
+        }
+        if (!keepView(v.n)) return;   // storeReaded: MyMulti keeps front-pattern views only (:237)
+        filesEachCameraFull[v.cam].push_back(v.file);
+        timestampFull[v.cam].push_back(v.timestamp);
+        timestampAvailable[v.cam].push_back(v.timestamp);
+        _omEachCamera[v.cam].push_back(om);
+        _tEachCamera[v.cam].push_back(tv);
+        std::vector<float> fi(v.img.size()), fo(v.obj.size());
+        for (size_t k = 0; k < v.img.size(); ++k) fi[k] = (float)v.img[k];
+        for (size_t k = 0; k < v.obj.size(); ++k) fo[k] = (float)v.obj[k];
+        _imagePointsForEachCamera[v.cam].push_back(std::move(fi));
+        _objectPointsForEachCamera[v.cam].push_back(std::move(fo));
+    };
+    std::vector<CornerView> batch;   // gpuPnP: every view of the run, in the order the host path meets them
     for (int cam = 0; cam < _nCamera; ++cam) {   // loadOneSerial (src/mymulticalib.cpp:262-301)
         const std::string folder = stg::resolve_path(dataFolder + "/" + cameraSerials[cam]);
         std::vector<std::string> files;
@@ -376,37 +420,43 @@ void MyMultiCameraCalibration::loadImages(const std::set<std::string>& outliers)
                 std::cout << "outlier:" << file << " skipped: " << std::endl;
                 continue;
             }
-            const int timestamp = std::stoi(fsys::path(file).stem().string());   // readTimestamps
-            stg::FileStorage fs(file, stg::FileStorage::READ);                    // readCorners
-            if (!fs.isOpened()) throw std::runtime_error("cannot read " + file);
-            const std::vector<double> img = points_of(fs["corners"], 2, file, "corners");
-            const std::vector<double> objd = points_of(fs["objects"], 3, file, "objects");
-            const int n = (int)img.size() / 2;
-            if ((int)objd.size() != 3 * n) throw std::runtime_error(file + ": corners and objects differ in count");
-            std::vector<double> obj(objd.size());   // objectPoints.convertTo(CV_32F)
-            for (size_t k = 0; k < objd.size(); ++k) obj[k] = (double)(float)objd[k];
-            double r[3], t[3];   // calcPatternPose: cv::solvePnP
-            if (mcc::pnp::solvePnP(obj.data(), img.data(), n, K, D, r, t) < 0)
-                throw std::runtime_error(file + ": too few corners for solvePnP");
-            const std::array<float, 3> om{(float)r[0], (float)r[1], (float)r[2]};
-            const std::array<float, 3> tv{(float)t[0], (float)t[1], (float)t[2]};
-            if (!is_valid_pose(tv.data())) {   // the reference asserts (src/mymulticalib.cpp:210, :297)
-                if (strictReference) strict_abort("isValidPose(tvec)", "src/mymulticalib.cpp:210 (calcPatternPose)");
-                ++invalidPoseCount;
-                std::cout << "invalid pattern :" << invalidPoseCount << ", " << file << std::endl;
+            CornerView v = read_view(cam, file);
+            if (gpuPnP) {
+                batch.push_back(std::move(v));
                 continue;
             }
-            if (!keepView(n)) continue;   // storeReaded: MyMulti keeps front-pattern views only (:237)
-            filesEachCameraFull[cam].push_back(file);
-            timestampFull[cam].push_back(timestamp);
-            timestampAvailable[cam].push_back(timestamp);
-            _omEachCamera[cam].push_back(om);
-            _tEachCamera[cam].push_back(tv);
-            std::vector<float> fi(img.size()), fo(obj.size());
-            for (size_t k = 0; k < img.size(); ++k) fi[k] = (float)img[k];
-            for (size_t k = 0; k < obj.size(); ++k) fo[k] = (float)obj[k];
-            _imagePointsForEachCamera[cam].push_back(std::move(fi));
-            _objectPointsForEachCamera[cam].push_back(std::move(fo));
+            double r[3], t[3];   // calcPatternPose: cv::solvePnP
+            if (mcc::pnp::solvePnP(v.obj.data(), v.img.data(), v.n, K, D, r, t) < 0)
+                throw std::runtime_error(file + ": too few corners for solvePnP");
+            store_view(v, r, t);
+        }
+    }
+    if (gpuPnP && !batch.empty()) {
+        // all poses in one launch (mcc_solve_pnp_batch), then the per-view sequence above in the same order
+        constexpr int kD = 12;   // every camera's coefficients, zero-padded as pnp.cpp::distort reads them
+        std::vector<double> K(9 * (size_t)_nCamera), D(kD * (size_t)_nCamera, 0.0);
+        for (int cam = 0; cam < _nCamera; ++cam) {
+            for (int k = 0; k < 9; ++k) K[9 * (size_t)cam + k] = _cameraMatrix[cam][k];
+            if ((int)_distortCoeffs[cam].size() > kD)
+                throw std::runtime_error("gpuPnP: more than 12 distortion coefficients (the tilted-sensor terms) are not supported");
+            for (size_t k = 0; k < _distortCoeffs[cam].size(); ++k) D[kD * (size_t)cam + k] = _distortCoeffs[cam][k];
+        }
+        std::vector<int> off(1, 0), cams;
+        std::vector<double> obj, img;
+        for (const CornerView& v : batch) {
+            off.push_back(off.back() + v.n);
+            cams.push_back(v.cam);
+            obj.insert(obj.end(), v.obj.begin(), v.obj.end());
+            img.insert(img.end(), v.img.begin(), v.img.end());
+        }
+        std::vector<double> rv, tv, rms;
+        std::vector<int> status;
+        mcc::pnp::solvePnPBatch(off, obj.data(), img.data(), cams.data(), _nCamera, K.data(), D.data(), kD, rv, tv, rms,
+                                status, 50, _device);
+        for (size_t i = 0; i < batch.size(); ++i) {
+            if (status[i] == MCC_PNP_TOO_FEW) throw std::runtime_error(batch[i].file + ": too few corners for solvePnP");
+            if (status[i] != MCC_PNP_SOLVED) throw std::runtime_error(batch[i].file + ": degenerate view for solvePnP");
+            store_view(batch[i], &rv[3 * i], &tv[3 * i]);
         }
     }
     // identifyMultiCameraTimestamps (src/mymulticalib.cpp:314-347)

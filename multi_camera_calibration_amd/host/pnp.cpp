@@ -5,6 +5,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <stdexcept>
+#include <string>
+
+#include "mcc.h"
 
 namespace mcc {
 namespace pnp {
@@ -399,6 +403,37 @@ double solvePnP(const double* object, const double* image, int n, const double K
     std::memcpy(rvec, r, sizeof r);
     std::memcpy(tvec, t, sizeof t);
     return err;
+}
+
+void solvePnPBatch(const std::vector<int>& view_off, const double* object, const double* image, const int* view_cam,
+                   int n_cams, const double* K, const double* D, int nd, std::vector<double>& rvec,
+                   std::vector<double>& tvec, std::vector<double>& rms, std::vector<int>& status, int max_iter,
+                   int device, double* device_ms) {
+    const int n_views = (int)view_off.size() - 1;
+    const size_t nv = n_views > 0 ? (size_t)n_views : 0;
+    rvec.assign(3 * nv, 0.0);
+    tvec.assign(3 * nv, 0.0);
+    rms.assign(nv, -1.0);
+    status.assign(nv, 0);
+    mcc_pnp_desc d{};
+    d.n_views = n_views;
+    d.view_off = view_off.data();
+    d.obj = object;
+    d.img = image;
+    d.view_cam = view_cam;
+    d.n_cams = n_cams;
+    d.K = K;
+    d.D = D;
+    d.nd = nd;
+    d.max_iter = max_iter;
+    d.device = device;
+    // (non-null outputs for an empty batch too: the library reports n_views <= 0 itself)
+    double dummy[3] = {0, 0, 0};
+    int idummy = 0;
+    const int rc = mcc_solve_pnp_batch(&d, nv ? rvec.data() : dummy, nv ? tvec.data() : dummy, nv ? rms.data() : dummy,
+                                       nv ? status.data() : &idummy, device_ms);
+    if (rc != MCC_OK)
+        throw std::runtime_error("mcc_solve_pnp_batch failed (" + std::to_string(rc) + "): " + mcc_last_error());
 }
 
 }  // namespace pnp

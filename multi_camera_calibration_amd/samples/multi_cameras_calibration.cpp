@@ -6,7 +6,7 @@
 //   multi_cameras_calibration --serials S0,S1,... --data DIR --config DIR [--doubleside FILE]
 //       [--front 8x11] [--back 7x10] [--out multi-camera-results.xml] [--single-pass]
 //       [--double-side] [--init-only] [--dump-problem FILE] [--dump-result FILE] [--device N]
-//       [--verbose]
+//       [--verbose] [--gpu-pnp]
 //
 // --double-side runs DoubleSideCalibration instead (the reference sample's #else branch: fixed
 // camera poses from the configs' CameraMatrix, the double-side transform optimised; its
@@ -18,6 +18,10 @@
 // "cameraIdx-timestamp.yaml" (imagePoints, objectPoints, imageSize); with --omni (the only camera
 // type whose intrinsics are restated) every camera is first calibrated by cv::omnidir::calibrate
 // on the GPU.  --cameras N (required), --min-matches K (nMiniMatches, default 20).
+//
+// --gpu-pnp seeds every view's pose on the GPU (MyMultiCameraCalibration::gpuPnP: one batched
+// solvePnP launch per loadImages, mcc::pnp::solvePnPBatch) where the default solves view by view on
+// the host; with it --init-only needs a GPU too.
 //
 // --init-only stops after loadImages + initialize (no GPU needed).  --dump-problem writes the
 // problem of the last pass (tests/cpp blob format + photo timestamps) with x0 = buildParaVector(),
@@ -108,7 +112,7 @@ void dump_problem(MultiCameraCalibration& mc, const std::string& path) {
 int main(int argc, char** argv) {
     std::string serials, data, config, ds, out = "multi-camera-results.xml", dump_p, dump_r, list;
     Size front(8, 11), back(7, 10);
-    bool single = false, init_only = false, double_side = false, omni = false;
+    bool single = false, init_only = false, double_side = false, omni = false, gpu_pnp = false;
     int device = 0, verbose = 0, ncams = 0, min_matches = 20;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -132,6 +136,7 @@ int main(int argc, char** argv) {
         else if (a == "--verbose") verbose = 1;
         else if (a == "--list") list = next();
         else if (a == "--omni") omni = true;
+        else if (a == "--gpu-pnp") gpu_pnp = true;
         else if (a == "--cameras") ncams = std::stoi(next());
         else if (a == "--min-matches") min_matches = std::stoi(next());
         else {
@@ -187,6 +192,7 @@ int main(int argc, char** argv) {
                                                   TermCriteria(TermCriteria::COUNT + TermCriteria::EPS, 200, 1e-7),
                                                   device));
         MyMultiCameraCalibration& multiCalib = *mc;
+        multiCalib.gpuPnP = gpu_pnp;
         multiCalib.loadImages();
         multiCalib.initialize();
         if (init_only) {
