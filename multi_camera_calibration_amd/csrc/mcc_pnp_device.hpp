@@ -238,6 +238,26 @@ MCC_PNP_FN void pnp_nearest_rotation(const double* M, double* R) {
     }
 }
 
+// pnp.cpp::log_near_pi: the rotation vector of R within 1e-5 rad of pi.  There cvRodrigues2 (rodrigues_m2v's
+// s < 1e-5, c <= 0 branch) takes the axis from sqrt((R_ii + 1) / 2) and the angle from acos(c), both good
+// to sqrt(eps) = 1e-8 only, which the closed-form pose (max_iter = 0) would carry.  Here the angle is
+// atan2(s, c) and the axis the column of (R + R^T) / 2 - c I = (1 - c) k k^T with the largest diagonal
+// entry, its sign from the skew part 2 s k (at s = 0, where r and -r are one rotation, the column's own).
+MCC_PNP_FN void pnp_log_near_pi(const double* R, double* r) {
+    const double vx = R[7] - R[5], vy = R[2] - R[6], vz = R[3] - R[1];
+    const double s = 0.5 * sqrt(vx * vx + vy * vy + vz * vz);
+    const double c = fmax(-1.0, fmin(1.0, (R[0] + R[4] + R[8] - 1) * 0.5));
+    const double d0 = R[0] - c, d1 = R[4] - c, d2 = R[8] - c;
+    const double o01 = 0.5 * (R[1] + R[3]), o02 = 0.5 * (R[2] + R[6]), o12 = 0.5 * (R[5] + R[7]);
+    const bool c0 = d0 >= d1 && d0 >= d2, c1 = !c0 && d1 >= d2;
+    const double k0 = c0 ? d0 : c1 ? o01 : o02, k1 = c0 ? o01 : c1 ? d1 : o12, k2 = c0 ? o02 : c1 ? o12 : d2;
+    double sc = atan2(s, c) / sqrt(k0 * k0 + k1 * k1 + k2 * k2);
+    if (k0 * vx + k1 * vy + k2 * vz < 0) sc = -sc;
+    r[0] = sc * k0;
+    r[1] = sc * k1;
+    r[2] = sc * k2;
+}
+
 // ---------------------------------------------------------------- the DLT's normal matrix, in LDS
 // Both DLTs have rows (h, 0, -u h) and (0, h, -v h) with h = (X, Y, 1) or (X, Y, Z, 1), so
 //   A^T A = [ S 0 -Su ; 0 S -Sv ; . . Sq ],  S* = sum w h h^T with w = 1, u, v, u^2 + v^2:
@@ -441,10 +461,15 @@ MCC_PNP_FN int pnp_solve_view(const double* obj, const double* img, int n, const
         C[4] = s[3]; C[5] = C[7] = s[4]; C[8] = s[5];
     }
     pnp_eig3(C, w, E);
-    const double wcap = 1e-9 * fmax(w[2], 1e-300);
-    const bool planar = w[0] <= wcap;
+    // A plane when the spread across it is below 3e-2 of the smaller spread within it (squared lengths: an
+    // rms relief of 17 % of the target's narrow side).  Below that the homography start is close enough for
+    // LM, which then works on the true points; the 12-vector DLT, whose normal matrix is nearly
+    // rank-deficient on a board that is slightly off its plane, is not: under 0.2 px noise it put LM into a
+    // wrong minimum, reported as solved, at ratios from 1e-9 up to 8e-3, and at none from 1.5e-2 up.
+    const bool planar = w[0] <= 3e-2 * fmax(w[1], 1e-300);
+    // the points lie on one line: no pose (first: on a line w0 and w1 are both rounding noise)
+    if (w[1] <= 1e-9 * fmax(w[2], 1e-300)) return kPnpDegenerate;
     if (!planar && n < 6) return kPnpTooFew;
-    if (w[1] <= wcap) return kPnpDegenerate;   // the points lie on one line: no pose
 
     for (int i = lane; i < n; i += MCC_PNP_LANES) {
         double x, y;
@@ -566,7 +591,9 @@ MCC_PNP_FN int pnp_solve_view(const double* obj, const double* img, int n, const
     }
     {
         double th, s, co;
-        rodrigues_m2v(R, r, th, s, co);
+        int near_pi;
+        rodrigues_m2v(R, r, th, s, co, near_pi);
+        if (near_pi) pnp_log_near_pi(R, r);
     }
     if (!pnp_finite6(r, t)) return kPnpDegenerate;
 

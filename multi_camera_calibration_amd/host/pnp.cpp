@@ -175,6 +175,28 @@ void homography(const double* XY, const double* xy, int n, double* H) {
         }
 }
 
+// The rotation vector of R within 1e-5 rad of pi, where rodriguesInv (cvRodrigues2's s < 1e-5, c <= 0
+// branch) takes the axis from sqrt((R_ii + 1) / 2) and the angle from acos(c), both good to sqrt(eps) = 1e-8
+// only.  The angle is atan2(s, c) and the axis the column of (R + R^T) / 2 - c I = (1 - c) k k^T with the
+// largest diagonal entry, its sign from the skew part 2 s k.  False (r untouched) away from pi.
+// csrc/mcc_pnp_device.hpp::pnp_log_near_pi is the same arithmetic.
+bool log_near_pi(const double* R, double* r) {
+    const double vx = R[7] - R[5], vy = R[2] - R[6], vz = R[3] - R[1];
+    if (!(std::sqrt((vx * vx + vy * vy + vz * vz) * 0.25) < 1e-5) || (R[0] + R[4] + R[8] - 1) * 0.5 > 0) return false;
+    const double s = 0.5 * std::sqrt(vx * vx + vy * vy + vz * vz);
+    const double c = std::fmax(-1.0, std::fmin(1.0, (R[0] + R[4] + R[8] - 1) * 0.5));
+    const double d0 = R[0] - c, d1 = R[4] - c, d2 = R[8] - c;
+    const double o01 = 0.5 * (R[1] + R[3]), o02 = 0.5 * (R[2] + R[6]), o12 = 0.5 * (R[5] + R[7]);
+    const bool c0 = d0 >= d1 && d0 >= d2, c1 = !c0 && d1 >= d2;
+    const double k0 = c0 ? d0 : c1 ? o01 : o02, k1 = c0 ? o01 : c1 ? d1 : o12, k2 = c0 ? o02 : c1 ? o12 : d2;
+    double sc = std::atan2(s, c) / std::sqrt(k0 * k0 + k1 * k1 + k2 * k2);
+    if (k0 * vx + k1 * vy + k2 * vz < 0) sc = -sc;
+    r[0] = sc * k0;
+    r[1] = sc * k1;
+    r[2] = sc * k2;
+    return true;
+}
+
 double rms_error(const double* object, const double* image, int n, const double* r, const double* t, const double* K,
                  const std::vector<double>& D, std::vector<double>& buf) {
     buf.resize(2 * (size_t)n);
@@ -277,7 +299,11 @@ double solvePnP(const double* object, const double* image, int n, const double K
     double w[3], V[9];
     jacobi_eig(C, 3, w, V);
     double R[9], t[3];
-    const bool planar = w[0] <= 1e-9 * std::max(w[2], 1e-300);
+    // A plane when the spread across it is below 3e-2 of the smaller spread within it (squared lengths: an
+    // rms relief of 17 % of the target's narrow side).  Below that the homography start is close enough for
+    // LM; the DLT, whose normal matrix is nearly rank-deficient on a board slightly off its plane, put LM
+    // into a wrong minimum at ratios from 1e-9 up to 8e-3.  csrc/mcc_pnp_device.hpp has the same test.
+    const bool planar = w[0] <= 3e-2 * std::max(w[1], 1e-300);
     if (planar) {
         // plane frame: Rp rows = (e2, e1, e0) (e0 = normal), X_plane = Rp (X - c)
         double Rp[9];
@@ -349,6 +375,7 @@ double solvePnP(const double* object, const double* image, int n, const double K
     }
     double r[3];
     rodriguesInv(R, r);
+    log_near_pi(R, r);
     // Levenberg-Marquardt on the reprojection error (numeric central-difference Jacobian)
     std::vector<double> buf, p0(2 * (size_t)n), pp(2 * (size_t)n), pm(2 * (size_t)n);
     double lambda = 1e-3;

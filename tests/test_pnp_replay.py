@@ -3,7 +3,10 @@
 tests/cpp/test_pnp_replay.cpp compiles csrc/mcc_pnp_device.hpp -- the code one wavefront of k_pnp runs
 for a view -- for the host with one lane (tests/cpp/hipstub stands in for the HIP header) and checks it on
 exact data against the truth (the C++ selftest's bounds, with and without the LM refinement), on noisy data
-against mcc::pnp::solvePnP (the same minimum), and on views that cannot be solved (status 1 and 2).  The
+against mcc::pnp::solvePnP (the same minimum), and on views that cannot be solved (status 1 and 2).  It also
+runs the pose, target and distortion lists of tests/test_pnp_generic.py and its near-planar relief sweep, so
+that a case that fails is known to be the arithmetic's before a GPU sees it, and holds pnp_rows, the analytic
+Jacobian, to central differences of pnp_residual entry by entry.  The
 lanes' summation order and the LDS phases exist only on the GPU: tests/test_pnp_batch.py covers those."""
 import os
 import subprocess
