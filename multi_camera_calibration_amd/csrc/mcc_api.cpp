@@ -21,6 +21,7 @@
 
 #include "../../include/mcc.h"
 #include "mcc_internal.h"
+#include "mcc_plan.hpp"
 
 using mcc::State;
 
@@ -53,6 +54,12 @@ struct DevBuf {
         if (e != hipSuccess) return e;
         if (count) e = hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice);
         return e;
+    }
+    // a host vector of T, or of a plain struct laid out like it (mcc::Int4 for int4)
+    template <typename U>
+    hipError_t upload(const std::vector<U>& h) {
+        static_assert(sizeof(U) == sizeof(T), "element layouts differ");
+        return upload(reinterpret_cast<const T*>(h.data()), h.size());
     }
     void release() {
         if (p) (void)hipFree(p);
@@ -96,96 +103,11 @@ StreamPool& stream_pool() {
     return *pool;
 }
 
-// Host restatement of cvRodrigues2 matrix -> vector (with the polar re-orthonormalisation)
-// used once per problem for fixed transforms (doubleSideTransform2vec,
-// src/mymulticalib.cpp:105-117; cameraPose2vec, src/doubleSide.cpp:262-275).
-void host_rodrigues_m2v(const double* Rin, double* r) {
-    double R[9];
-    std::memcpy(R, Rin, sizeof(R));
-    for (int it = 0; it < 40; ++it) {
-        double cof[9] = {R[4] * R[8] - R[5] * R[7], -(R[3] * R[8] - R[5] * R[6]), R[3] * R[7] - R[4] * R[6],
-                         -(R[1] * R[8] - R[2] * R[7]), R[0] * R[8] - R[2] * R[6], -(R[0] * R[7] - R[1] * R[6]),
-                         R[1] * R[5] - R[2] * R[4], -(R[0] * R[5] - R[2] * R[3]), R[0] * R[4] - R[1] * R[3]};
-        double d = R[0] * cof[0] + R[1] * cof[1] + R[2] * cof[2], delta = 0;
-        if (!(std::fabs(d) > 1e-300)) break;
-        for (int k = 0; k < 9; ++k) {
-            double v = 0.5 * (R[k] + cof[k] / d);
-            delta = std::max(delta, std::fabs(v - R[k]));
-            R[k] = v;
-        }
-        if (delta < 1e-15) break;
-    }
-    double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
-    double s = std::sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
-    double c = (R[0] + R[4] + R[8] - 1) * 0.5;
-    c = c > 1. ? 1. : c < -1. ? -1. : c;
-    double theta = std::acos(c);
-    if (s < 1e-5) {
-        if (c > 0) {
-            rx = ry = rz = 0;
-        } else {
-            double t;
-            t = (R[0] + 1) * 0.5; rx = std::sqrt(std::max(t, 0.));
-            t = (R[4] + 1) * 0.5; ry = std::sqrt(std::max(t, 0.)) * (R[1] < 0 ? -1. : 1.);
-            t = (R[8] + 1) * 0.5; rz = std::sqrt(std::max(t, 0.)) * (R[2] < 0 ? -1. : 1.);
-            if (std::fabs(rx) < std::fabs(ry) && std::fabs(rx) < std::fabs(rz) && (R[5] > 0) != (ry * rz > 0)) rz = -rz;
-            theta /= std::sqrt(rx * rx + ry * ry + rz * rz);
-            rx *= theta; ry *= theta; rz *= theta;
-        }
-    } else {
-        double vth = 1 / (2 * s) * theta;
-        rx *= vth; ry *= vth; rz *= vth;
-    }
-    r[0] = rx; r[1] = ry; r[2] = rz;
-}
-
-// computeTiltProjectionMatrix (OpenCV calib3d, distortion_model.hpp) for the tilted-sensor model of
-// cv::projectPoints with 14 coefficients, which src/mymulticalib.cpp:566 reaches with whatever
-// Distortion the camera XML holds (:118-132): matTilt = matProjZ * (matRotY * matRotX), row-major,
-// Matx products summed left to right from 0
-void tilt_matrix(double tx, double ty, double M[9]) {
-    const double cx = std::cos(tx), sx = std::sin(tx), cy = std::cos(ty), sy = std::sin(ty);
-    const double rx[9] = {1, 0, 0, 0, cx, sx, 0, -sx, cx};
-    const double ry[9] = {cy, 0, -sy, 0, 1, 0, sy, 0, cy};
-    double rxy[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s = 0;
-            for (int k = 0; k < 3; ++k) s += ry[3 * i + k] * rx[3 * k + j];
-            rxy[3 * i + j] = s;
-        }
-    const double pz[9] = {rxy[8], 0, -rxy[2], 0, rxy[8], -rxy[5], 0, 0, 1};
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s = 0;
-            for (int k = 0; k < 3; ++k) s += pz[3 * i + k] * rxy[3 * k + j];
-            M[3 * i + j] = s;
-        }
-}
-
 }  // namespace
 
-struct mcc_problem {
-    int model = 0, C = 0, V = 0, E = 0, nd = 0, m = 0, P = 0, device = 0;
-    long long corners = 0;
-    bool rational = false;
-    int prism = 0;   // 1: thin prism s1..s4, 2: + the tilted sensor (nd = 14, tau != 0)
-    int has_back = 0;
-    int max_epp = 1, nblk = 0, n_items = 0, n_pairs = 0, n_norm_chunks = 0;
-    size_t n_pair_doubles = 0;   // Schur pair-product slots (36 or 48 doubles each)
-    // split step's k_photo groups (consecutive photos) and their pair / contribution lists
-    int n_pgroups = 0, max_gpairs = 0, max_gcon = 0, max_gedges = 0;
-    size_t photo_shmem = 0;
-    // split step as ONE fused kernel per group (k_group: photo update, edge prologues, sweep, chain,
-    // photo Schur work) instead of k_prep -> k_edge -> k_photo; MCC_GROUP=0 selects the three
-    int use_group = 1;
-    size_t group_shmem = 0;
-    int group_lanes = 32;   // k_group's lanes per edge (32: 512-thread workgroups; 16: 256)
-    // fused single-kernel step (m <= kFusedMaxM): photo contributions + two-level reduction
-    static constexpr int kFusedMaxM = 30;
-    int fused = 0, group_size = 1, n_groups = 1;
-    // m > 30 (or MCC_FUSED=0): the split step k_prep -> k_edge -> k_photo -> k_schur -> k_solve
-    int max_cpp = 1;   // most corners of one photo
+// The plan's scalars (mcc_plan.hpp: the sizes, the step's form, the switches), then what lives on the device.
+struct mcc_problem : mcc::PlanScalars {
+    int device = 0;
     hipStream_t stream = nullptr;
 
     // host-side maps
@@ -206,63 +128,28 @@ struct mcc_problem {
     DevBuf<int> ghdr;        // k_group's per-group headers [n_pgroups][kGHdrInts] (LinArgs::ghdr)
     DevBuf<double> kintr;    // the cameras' intrinsics rows in FP64 [C][kGIntr] (LinArgs::kintr)
     DevBuf<int> prep_ptr, prep_edge;   // k_prep4's groups (three-kernel split step)
-    // MCC_POISON_HANDOFF=1 (test): every buffer handed between workgroups inside one launch or
-    // between the step's kernels is filled with NaN (all-ones bytes) before each step, so that a
-    // read of a word its producer has not yet stored this step shows up in the result
-    bool poison = false;
-    int poison_level = 0;
-    bool peer_push = true;   // m > 30 with the peer transport: k_peer_push sends from many workgroups
-    int schur_one_level = 0; // k_schur's single hand-off level (m <= 30; MCC_SCHUR_ONE_LEVEL=0 restores two)
-    int n_prep = 0, prep_lanes = 1;   // MCC_PREP_LANES=4: k_prep4 (measured slower at configs 3 and 5)
-    // warm solve (m > 30 split step, MCC_WARM=0 turns it off): a resident helper kernel on a side
-    // stream (one per batch of update steps) inverts each step's reduced system while the next step
-    // linearises; the next k_solve refines with it (WarmCtx, mcc_internal.h)
-    bool warm = false;
+    // the m > 30 warm solve (PlanScalars::warm)
     hipStream_t side = nullptr;      // the helper's stream
     double* sinv = nullptr;          // [M x M] the helper's S^-1 (ordinary memory)
     double* prev2 = nullptr;         // uncached: [2][prev_stride] k_schur's copies of [S | r] (iteration parity)
-    int prev_stride = 0;
     unsigned* wsync = nullptr;       // uncached: [8] epochs, stop, the helper's PD flag; its refined epoch, status, corrections
     double* xsol = nullptr;          // uncached: [128] the helper's solution (helper_refine)
-    bool helper_refine = false;      // single GPU, m > 30: the helper refines too (MCC_HELPER_REFINE)
-    // k_schur publishes the system at its start and the helper polls prev2's words as the blocks land
-    // (config3, three-kernel step: 108.4-109.1 -> 107.4-107.6 us per step), else at its end and the helper
-    // stages in one batch (k_group's step: config3's 8-rank shard, whose step the helper's cycle bounds,
-    // was 0.9 us slower polled); MCC_HELPER_POLL=0/1 forces either
-    int helper_early = 0;
-    int inv_la = 0;                  // the helper's look-ahead inversion (WarmCtx::inv_la): the k_group path
     DevBuf<long long> warm_stats;    // [5] (mcc_solve_stats)
-    int warm_poison = 0;             // MCC_WARM_POISON=1 (test): the helper publishes NaN inverses
-    // k_solve's bound on the wait for the helper (MCC_WARM_TIMEOUT_MS, default 10 s; a step that hits
-    // it fails with MCC_ETIMEOUT), the helper's idle exit (the wait bound plus the peer timeout: a
-    // k_solve may sit in a peer exchange before it publishes), the test delay (MCC_WARM_DELAY_US)
-    long long warm_wait_ticks = 1000000000LL, warm_idle_ticks = 4000000000LL, warm_delay_ticks = 0;
-    long long spare_delay_ticks = 0;  // MCC_SPARE_DELAY_US (test): the fused step's spare starts this late
-    bool small_stats = false;         // MCC_SOLVE_STATS=1: count the m <= 30 warm solves (SolveCtx::sstats)
-    // k_group's step with k_schur's reduction and the solve folded into the same launch (LinArgs::fold;
-    // MCC_GFOLD=0 keeps k_group -> k_schur): fnorm [4V] and fiv [m^2 + 1] hand-off words, kFoldEmpty
-    // between launches like the slots and the item partials
-    bool gfold = false;
-    int fold_direct = 0;   // the final workgroup sums where the words land (LinArgs::fold_direct)
-    int fold_dyn = 0;      // the groups take the reduction's tasks as they finish (LinArgs::fold_dyn)
-    int fold_first = 0;    // MCC_FOLD_CONSUMERS_FIRST=1 (test): LinArgs::fold_first
+    // the folded step (PlanScalars::gfold)
     DevBuf<int> fold_ticket;
-    int max_item_slots = 0;
     DevBuf<double> fnorm, fiv;
-    int fault_photo = -1;            // MCC_FAULT_PHOTO (test): LinArgs::fault_photo
     DevBuf<unsigned char> edge_lphoto;
     DevBuf<unsigned> gcon;
     DevBuf<int4> edge_info, items, gpairs;
     DevBuf<State> state;
     State* h_state = nullptr;   // pinned staging
     float* h_x = nullptr;       // [P] pinned staging of mcc_optimize's parameters (allocated on first use)
-    int packed_len = 0, ntri = 0;
 
     // graphs: gexec[k] = 2^k update steps (k < kGraphSizes), built on first use; a run of n steps
     // is launched as the binary decomposition of n (20 steps: two launches, 16 + 4).
     // mcc_optimize polls the device stop test every kGraphSteps steps.
     static constexpr int kGraphSteps = 8;
-    static constexpr int kGraphSizes = 7;   // up to 64 steps per launch
+    static constexpr int kGraphSizes = mcc::kGraphSizes;   // up to 64 steps per launch
     hipGraphExec_t gexec[kGraphSizes] = {};
     // mcc_timing_linearize: a graph of lin_graph_n launches of the split step's linearisation kernels
     hipGraphExec_t lin_graph = nullptr;
@@ -271,8 +158,6 @@ struct mcc_problem {
     // pending update again and rewrites Y' and z' at the drifted parameters
     DevBuf<float> xsave;
     DevBuf<double> ysave, zpsave;
-    int graph_sizes = kGraphSizes;   // MCC_GRAPH_SIZES (A/B of the launch granularity)
-    bool use_graph = true;
     // the device State is in free-running mode (crit_type 0) since the last mcc_step: later
     // mcc_step calls enqueue without a host round trip (set_state clears it)
     bool stepping = false;
@@ -289,7 +174,6 @@ struct mcc_problem {
     double* peer_scratch = nullptr;          // [4] handshake / max
     int peer_n = 0;                          // ranks of an initialised transport
     bool peer_on = false;
-    long long peer_timeout = 0;              // s_memrealtime ticks
 
     // timing window
     bool timing = false;
@@ -742,43 +626,24 @@ const char* mcc_last_error(void) { return g_err.c_str(); }
 // the other C-ABI translation units (mcc_omnicalib_api.cpp) report through the same message slot
 __attribute__((visibility("hidden"))) int mcc_internal_fail(int code, const char* msg) { return fail(code, msg); }
 __attribute__((visibility("hidden"))) void mcc_internal_rodrigues_m2v(const double* R, double* r) {
-    host_rodrigues_m2v(R, r);
+    mcc::host_rodrigues_m2v(R, r);
 }
 
 int mcc_nparams(const mcc_problem* p) { return p ? p->P : 0; }
 int mcc_global_dim(const mcc_problem* p) { return p ? p->m : 0; }
 
+// Validation and the plan (mcc_plan.cpp: the step's form, every index structure) are host-only work
+// on the descriptor; what is left here is the device: the CU count the plan's rules take, the three
+// LDS limits that depend on the chosen form, the uploads and the allocations.
 int mcc_create(mcc_problem** out, const mcc_desc* d) {
     if (!out || !d) return fail(MCC_EINVAL, "null argument");
     *out = nullptr;
-    if (d->model < 0 || d->model > 2) return fail(MCC_EINVAL, "unknown model");
-    if (d->n_cams < 1 || d->n_photos < 0 || d->n_edges < 0) return fail(MCC_EINVAL, "bad sizes");
-    // the reference's meanReProjError is 0 / 0 without observations (src/multicalib.cpp:989), and
-    // a photo vertex exists only through an edge (getPhotoVertex, :323-346); a rank of a sharded
-    // problem needs photos of its own to take part in the per-step exchange
-    if (d->n_photos < 1 || d->n_edges < 1) return fail(MCC_EINVAL, "no photo vertices / observations");
-    if (d->model != MCC_MODEL_DOUBLESIDE && d->n_cams < 2) return fail(MCC_EINVAL, "need >= 2 cameras");
-    if (d->model == MCC_MODEL_OMNI && (d->nd != 4 || !d->xi)) return fail(MCC_EINVAL, "omni needs nd == 4 and xi");
-    if (d->model != MCC_MODEL_OMNI && !(d->nd == 4 || d->nd == 5 || d->nd == 8 || d->nd == 12 || d->nd == 14))
-        return fail(MCC_EINVAL, "pinhole nd must be 4, 5, 8, 12 or 14");
-    if (d->model == MCC_MODEL_DOUBLESIDE && !d->cam_pose) return fail(MCC_EINVAL, "DOUBLESIDE needs cam_pose");
-    const int C = d->n_cams, V = d->n_photos, E = d->n_edges;
-    for (int e = 0; e < E; ++e) {
-        if (d->edge_cam[e] < 0 || d->edge_cam[e] >= C || d->edge_photo[e] < 0 || d->edge_photo[e] >= V ||
-            d->edge_n[e] < 1 || d->edge_off[e] < 0)
-            return fail(MCC_EINVAL, "edge " + std::to_string(e) + " out of range");
-        if (d->edge_n[e] > 1024) return fail(MCC_EINVAL, "more than 1024 corners in an edge");
-        int side = d->edge_side ? d->edge_side[e] : MCC_FRONT;
-        if (side == MCC_BACK && d->model == MCC_MODEL_PINHOLE && !d->ds_pose)
-            return fail(MCC_EINVAL, "BACK edge without doubleSideTransform (the reference dereferences an empty Mat)");
-        if (side == MCC_BACK && d->model == MCC_MODEL_OMNI) return fail(MCC_EINVAL, "BACK edges are pinhole only");
-    }
+    const mcc::Options opt = mcc::Options::from_env([](const char* name) -> const char* { return std::getenv(name); });
+    std::string why;
+    if (int rc = mcc::validate(*d, &why)) return fail(rc, why);
 
     mcc_problem* p = new mcc_problem();
-    p->model = d->model; p->C = C; p->V = V; p->E = E; p->nd = d->nd; p->device = d->device;
-    p->m = d->model == MCC_MODEL_DOUBLESIDE ? 6 : 6 * (C - 1);
-    p->P = p->m + 6 * V;
-    int rc = MCC_OK;
+    p->device = d->device;
     auto bail = [&](int code) { mcc_destroy(p); return code; };
 #define HIPC(expr)                                                                          \
     do {                                                                                    \
@@ -788,375 +653,63 @@ int mcc_create(mcc_problem** out, const mcc_desc* d) {
     } while (0)
     HIPC(hipSetDevice(d->device));
     HIPC(stream_pool().take(d->device, &p->stream));
-    if (const char* g = std::getenv("MCC_GRAPH")) p->use_graph = std::atoi(g) != 0;
-    if (const char* g = std::getenv("MCC_GRAPH_SIZES"))
-        p->graph_sizes = std::min(mcc_problem::kGraphSizes, std::max(1, std::atoi(g)));
+    int n_cu_dev = 256;
+    if (hipDeviceGetAttribute(&n_cu_dev, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || n_cu_dev <= 0)
+        n_cu_dev = 256;
+    mcc::Plan plan;
+    if (int rc = mcc::plan_problem(*d, opt, opt.cus > 0 ? opt.cus : n_cu_dev, n_cu_dev, &plan, &why))
+        return bail(fail(rc, why));
+    static_cast<mcc::PlanScalars&>(*p) = plan;
+    const int C = p->C, V = p->V, E = p->E;
+    if (p->fused && mcc_lin_shmem(p->max_epp, C, p->m, p->max_cpp) > 160 * 1024)
+        return bail(fail(MCC_EINVAL, "too many edges / corners per photo for the LDS staging"));
+    if (!p->fused && !p->use_group && p->photo_shmem > 160 * 1024)
+        return bail(fail(MCC_EINVAL, "too many Schur pairs of one photo for k_photo's LDS"));
+    if (!p->fused && p->use_group && p->group_shmem > 160 * 1024)
+        return bail(fail(MCC_EINVAL, "too many edges / Schur pairs of one photo group for k_group's LDS"));
 
-    // distortion specialisation (zero coefficients are exact no-ops in OpenCV's formula)
-    if (d->model != MCC_MODEL_OMNI) {
-        for (int c = 0; c < C; ++c)
-            for (int q = 5; q < std::min(d->nd, 12); ++q) {
-                const float v = d->D[d->nd * c + q];
-                if (v != 0.f) {
-                    if (q < 8) p->rational = true;
-                    else p->prism = 1;
-                }
-            }
-        // the tilted sensor (tau_x, tau_y: D[12], D[13] of 14): matTilt per camera in FP64, as
-        // cvProjectPoints2Internal forms it from the CV_32F coefficients (identity where tau = 0, which
-        // the projection then applies exactly: vecTilt = (xd0, yd0, 1), invProj = 1)
-        bool tilt = false;
-        for (int c = 0; c < C && d->nd == 14; ++c)
-            tilt = tilt || d->D[14 * c + 12] != 0.f || d->D[14 * c + 13] != 0.f;
-        if (tilt) {
-            p->rational = true;   // zero k4..k6 / s1..s4 are exact no-ops in the 14-term formula
-            p->prism = 2;
-            std::vector<double> mt(9 * (size_t)C);
-            for (int c = 0; c < C; ++c) tilt_matrix(d->D[14 * c + 12], d->D[14 * c + 13], mt.data() + 9 * c);
-            HIPC(p->tilt.upload(mt.data(), mt.size()));
-        }
+    // ---- the plan's arrays
+    p->dev2ref_edge = std::move(plan.dev2ref_edge);
+    p->dev2ref_corner = std::move(plan.dev2ref_corner);
+    p->edge_n_dev = std::move(plan.edge_n_dev);
+    static_assert(sizeof(mcc::Int4) == sizeof(int4), "Plan's Int4 arrays upload as int4");
+    HIPC(p->obj_x.upload(plan.obj_x)); HIPC(p->obj_y.upload(plan.obj_y)); HIPC(p->obj_z.upload(plan.obj_z));
+    HIPC(p->img_u.upload(plan.img_u)); HIPC(p->img_v.upload(plan.img_v));
+    HIPC(p->edge_info.upload(plan.info));
+    HIPC(p->edge_gblock.upload(plan.gblock));
+    HIPC(p->edge_photo.upload(plan.ephoto));
+    HIPC(p->photo_ptr.upload(plan.photo_ptr));
+    HIPC(p->photo_corner.upload(plan.photo_corner));
+    if (p->prism == 2) HIPC(p->tilt.upload(plan.tilt));
+    HIPC(p->cam_rt.upload(plan.cam_rt));
+    HIPC(p->ds_rt.upload(plan.ds_rt));
+    HIPC(p->alpha.upload(plan.alpha));
+    HIPC(p->pgrp_ptr.upload(plan.pgrp_ptr));
+    HIPC(p->pgrp_edge.upload(plan.pgrp_edge));
+    HIPC(p->edge_lphoto.upload(plan.edge_lphoto));
+    HIPC(p->ghdr.upload(plan.ghdr));
+    HIPC(p->kintr.upload(plan.kintr));
+    if (p->n_prep) {
+        HIPC(p->prep_ptr.upload(plan.prep_ptr));
+        HIPC(p->prep_edge.upload(plan.prep_edge));
     }
-
-    // ---- photo-major edge order (stable within a photo: reference edge order)
-    std::vector<int> order(E);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d->edge_photo[a] < d->edge_photo[b]; });
-    p->dev2ref_edge = order;
-    std::vector<int> photo_ptr(V + 1, 0);
-    for (int e = 0; e < E; ++e) photo_ptr[d->edge_photo[e] + 1]++;
-    for (int v = 0; v < V; ++v) {
-        p->max_epp = std::max(p->max_epp, photo_ptr[v + 1]);
-        photo_ptr[v + 1] += photo_ptr[v];
-    }
-    long long ncorner = 0;
-    for (int e = 0; e < E; ++e) ncorner += d->edge_n[e];
-    p->corners = ncorner;
-    std::vector<float> ox(ncorner), oy(ncorner), oz(ncorner), iu(ncorner), iv(ncorner);
-    std::vector<int4> info(E);
-    std::vector<int> gblock(E), ephoto(E);
-    p->dev2ref_corner.resize(ncorner);
-    p->edge_n_dev.resize(E);
-    long long off = 0;
-    for (int de = 0; de < E; ++de) {
-        const int e = order[de], n = d->edge_n[e];
-        const int side = d->edge_side ? d->edge_side[e] : MCC_FRONT;
-        for (int i = 0; i < n; ++i) {
-            const long long s = (long long)d->edge_off[e] + i;
-            ox[off + i] = d->obj[3 * s]; oy[off + i] = d->obj[3 * s + 1]; oz[off + i] = d->obj[3 * s + 2];
-            iu[off + i] = d->img[2 * s]; iv[off + i] = d->img[2 * s + 1];
-            p->dev2ref_corner[off + i] = s;
-        }
-        info[de] = make_int4(d->edge_cam[e], side, (int)off, n);
-        if (side == MCC_BACK) p->has_back = 1;
-        ephoto[de] = d->edge_photo[e];
-        p->edge_n_dev[de] = n;
-        if (d->model == MCC_MODEL_DOUBLESIDE) gblock[de] = side == MCC_BACK ? 0 : -1;
-        else gblock[de] = d->edge_cam[e] - 1;
-        off += n;
-    }
-    std::vector<int> photo_corner(V + 1, 0);
-    for (int v = 0; v < V; ++v) {
-        photo_corner[v + 1] = photo_corner[v];
-        for (int de = photo_ptr[v]; de < photo_ptr[v + 1]; ++de) photo_corner[v + 1] += info[de].w;
-        p->max_cpp = std::max(p->max_cpp, photo_corner[v + 1] - photo_corner[v]);
-    }
-
-    // small camera blocks and at most two photo workgroups per CU (the fused kernel's occupancy):
-    // one kernel per Gauss-Newton step.  More photos than that run the fused kernel's serial
-    // per-photo chain in several rounds, and the split step is faster (config4, 1000 views:
-    // 43.3 vs 47.4 us; config2, 500 views: 38.2 vs 25.9 us).  MCC_FUSED=1 / 0 forces either.
-    int n_cu = 256;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || n_cu <= 0)
-        n_cu = 256;
-    const int n_cu_dev = n_cu;   // the device's own (the folded step's progress rule below)
-    if (const char* f = std::getenv("MCC_CUS")) n_cu = std::max(1, std::atoi(f));   // test: the path rules at another CU count
-    // (the tilted sensor takes the split step: the fused kernel's PRISM variants already hold 256 VGPRs,
-    // and the tilt's per-corner 3 x 3 map and 2 x 2 chain spill there; k_group / k_edge have room)
-    const bool fusable = p->m <= mcc_problem::kFusedMaxM && V > 0 && p->max_epp <= 64 && p->prism != 2;
-    p->fused = fusable && V <= 2 * n_cu;
-
-    // ---- Schur pair lists.  The split step's photo work (k_group / k_photo) takes groups of
-    // consecutive photos (at most kPhotoGroup photos and the cap's edges) and sums the group's pair
-    // products per camera-pair block: one slot per (group, block), block-major over the groups,
-    // k_schur sums a block's slots in order.  A contribution is one ordered edge pair (e1, e2) of a
-    // photo with gblock(e1) <= gblock(e2) (both orders within one block), in photo then edge order.
-    const int nb = p->m / 6;
-    p->nblk = nb * (nb + 1) / 2;
-    auto blk_index = [nb](int b1, int b2) { return b1 * nb - b1 * (b1 - 1) / 2 + (b2 - b1); };
-    auto make_groups = [&](int cap) {
-        std::vector<int> g(1, 0);
-        for (int v = 0; v < V;) {
-            int w = v, edges = 0;
-            while (w < V && w - v < mcc::kPhotoGroup &&
-                   (w == v || edges + (photo_ptr[w + 1] - photo_ptr[w]) <= cap)) {
-                edges += photo_ptr[w + 1] - photo_ptr[w];
-                ++w;
-            }
-            g.push_back(w);
-            v = w;
-        }
-        return g;
-    };
-    // k_group takes groups of at most kGroupRound edges (one 16-edge round per workgroup; config4's
-    // 1 000 photos -> 250 workgroups, one per CU); k_photo's groups sum more photos (<= 64 edges).
-    // k_group (two workgroups per CU) wins while its groups fit the CUs in one wave of workgroups
-    // (config4: 32.3 vs 36.9 us per step); with more groups the three-kernel form's higher
-    // occupancy wins (config5: 67.3 vs 61.0, config3: 185.5 vs 120.5).  MCC_GROUP=1 / 0 forces.
-    int group_cap = mcc::kGroupRound;   // MCC_GROUP_EDGES: k_group's edges per group (A/B; > 16: several rounds)
-    const char* gcap_env = std::getenv("MCC_GROUP_EDGES");
-    if (gcap_env) group_cap = std::max(1, std::min(4 * mcc::kGroupRound, std::atoi(gcap_env)));
-    std::vector<int> pgrp_ptr = make_groups(group_cap);
-    // More 16-edge groups than CUs: wider groups (up to two 16-edge rounds each) while that brings them
-    // within one wave of workgroups -- a second wave of groups costs a whole group chain, a second
-    // round inside a group only its edge phases (config3's 8-rank shard, 625 views / 4 871 edges:
-    // 313 groups of 16 -> 244 of <= 24 edges, 58.4 -> 47.4 us per step against the three kernels;
-    // at 64 edges config5's 2 000 views take 65.0 vs 60.2 us, so the widening stops at 32)
-    for (int cap = mcc::kGroupRound + 8; !gcap_env && (int)pgrp_ptr.size() - 1 > n_cu && cap <= 2 * mcc::kGroupRound;
-         cap += 8) {
-        std::vector<int> g = make_groups(cap);
-        if ((int)g.size() - 1 <= n_cu) {
-            pgrp_ptr = std::move(g);
-            group_cap = cap;
-        }
-    }
-    // The fused kernel runs a photo's edges one per wave on its four waves, so photos with more than
-    // four edges take it through several dependent rounds; k_group spreads a group's 16 edges over its
-    // eight waves in one.  With more than four edges per photo and k_group's groups within the CUs the
-    // split step wins (config5's 500-view shard, 8 edges per photo: 28.9 vs 32.5 us per step).
-    if (p->fused && p->max_epp > 4 && (int)pgrp_ptr.size() - 1 <= n_cu) p->fused = false;
-    if (const char* f = std::getenv("MCC_FUSED")) p->fused = fusable && std::atoi(f) != 0;
-    if (!p->fused && p->max_epp > 64)
-        return bail(fail(MCC_EINVAL, "more than 64 edges (camera observations) of one photo vertex"));
-    p->use_group = !p->fused && (int)pgrp_ptr.size() - 1 <= n_cu;
-    if (const char* f = std::getenv("MCC_GROUP")) p->use_group = !p->fused && std::atoi(f) != 0;
-    if (!p->use_group) pgrp_ptr = make_groups(mcc::kPhotoGroupEdges);
-    if (const char* f = std::getenv("MCC_GROUP_LANES")) p->group_lanes = std::atoi(f) == 16 ? 16 : 32;
-    if (const char* f = std::getenv("MCC_PEER_PUSH")) p->peer_push = std::atoi(f) != 0;
-    if (const char* f = std::getenv("MCC_POISON_HANDOFF")) {
-        p->poison_level = std::atoi(f);
-        p->poison = p->poison_level != 0;
-    }
-    const int NG = (int)pgrp_ptr.size() - 1;
-    std::vector<int4> gpairs;                           // {first contribution, count, diagonal << 1, slot}
-    std::vector<unsigned> gcon;
-    std::vector<int> gpair_ptr(NG + 1, 0), gcon_ptr(NG + 1, 0);
-    std::vector<std::vector<int>> blk_src(p->nblk);   // each block's gpairs, group order
-    std::vector<std::vector<unsigned>> per_blk(p->nblk);
-    for (int g = 0; g < NG; ++g) {
-        const int ge0 = photo_ptr[pgrp_ptr[g]];
-        std::vector<int> used;
-        for (int v = pgrp_ptr[g]; v < pgrp_ptr[g + 1]; ++v)
-            for (int e1 = photo_ptr[v]; e1 < photo_ptr[v + 1]; ++e1) {
-                if (gblock[e1] < 0) continue;
-                for (int e2 = photo_ptr[v]; e2 < photo_ptr[v + 1]; ++e2) {
-                    if (gblock[e2] < 0 || gblock[e1] > gblock[e2]) continue;
-                    const int b = blk_index(gblock[e1], gblock[e2]);
-                    if (per_blk[b].empty()) used.push_back(b);
-                    per_blk[b].push_back((unsigned)(e1 - ge0) | ((unsigned)(e2 - ge0) << 8) |
-                                         ((e1 == e2 ? 1u : 0u) << 16) | ((unsigned)(v - pgrp_ptr[g]) << 17));
-                }
-            }
-        // the group's block pairs by contribution count, largest first: k_photo's pair tasks of a
-        // wave step through their contributions in lock-step, so each wave should hold pairs of
-        // similar counts (config3: 15.5 -> 10.8 iterations on a group's busiest wave).  Outputs
-        // are unchanged: a pair's slot offset travels with it.
-        std::sort(used.begin(), used.end(), [&](int x, int y) {
-            return per_blk[x].size() != per_blk[y].size() ? per_blk[x].size() > per_blk[y].size() : x < y;
-        });
-        const int cbase = (int)gcon.size();
-        for (int b : used) {
-            blk_src[b].push_back((int)gpairs.size());
-            const int b1 = [&] { int r = 0; while (r + 1 < nb && blk_index(r + 1, r + 1) <= b) ++r; return r; }();
-            gpairs.push_back(make_int4((int)gcon.size() - cbase, (int)per_blk[b].size(), blk_index(b1, b1) == b ? 2 : 0, -1));
-            gcon.insert(gcon.end(), per_blk[b].begin(), per_blk[b].end());
-            per_blk[b].clear();
-        }
-        gpair_ptr[g + 1] = (int)gpairs.size();
-        gcon_ptr[g + 1] = (int)gcon.size();
-        p->max_gpairs = std::max(p->max_gpairs, gpair_ptr[g + 1] - gpair_ptr[g]);
-        p->max_gcon = std::max(p->max_gcon, gcon_ptr[g + 1] - gcon_ptr[g]);
-        p->max_gedges = std::max(p->max_gedges, photo_ptr[pgrp_ptr[g + 1]] - ge0);
-    }
-    p->n_pgroups = NG;
-    p->photo_shmem = mcc::photo_lds_bytes(p->max_gedges, p->max_gpairs, p->max_gcon);
-    p->group_shmem = mcc::group_lds_bytes(p->max_gedges, C, p->max_gpairs, p->max_gcon);
-    std::vector<int4> items;
-    std::vector<int> block_items(p->nblk + 1, 0);
-    // slot sizes: 48 doubles on a diagonal camera-pair block (S entries, r, JTE), 36 off the
-    // diagonal (no self pair there, so r and JTE would be zeros); pair .w = the slot's offset in
-    // doubles; item = {block, first slot's offset, slots, slot size}
-    int n_slots = 0;
-    size_t n_doubles = 0;
-    // m <= 30 with several camera-pair blocks (one hand-off level: the final arriver loads every
-    // item's partial in one batch, so more items cost it little): 64 slots per item, four items per
-    // 250-slot block at config4 -- 28.4-28.6 vs 29.1-29.2 us per step with 320 (interleaved, round 4;
-    // 32: 28.7-28.8, 16: 30.7).  config5's single block (DoubleSide, m = 6) keeps 320 (60.5-60.7 vs
-    // 60.8-60.9 at 64)
-    int min_slots = p->m <= 30 && p->nblk > 1 ? 64 : 320;
-    if (const char* f = std::getenv("MCC_ITEM_SLOTS")) min_slots = std::max(1, std::atoi(f));
-    for (int b = 0; b < p->nblk; ++b) {
-        int b1 = 0;
-        while (b1 + 1 < nb && blk_index(b1 + 1, b1 + 1) <= b) ++b1;
-        const int stride = blk_index(b1, b1) == b ? 48 : 36;
-        const int begin = n_slots;
-        const size_t base = n_doubles;
-        for (int src : blk_src[b]) {
-            gpairs[src].w = (int)n_doubles;
-            n_doubles += stride;
-            ++n_slots;
-        }
-        if (n_doubles > (size_t)INT32_MAX) return bail(fail(MCC_EINVAL, "too many Schur pairs"));
-        const int end = n_slots;
-        // <= 24 work items per block keeps the last-arriver assembly short; >= min_slots slots per
-        // item (MCC_ITEM_SLOTS, default 320) amortises an item's fixed latency (one load round trip, the
-        // write-through hand-off and ticket) over more slots (config3, interleaved: 160 -> 320 slots
-        // 120.8 -> 119.6 us per step, 640 122.3; configs 4 and 5 within noise)
-        // A block of at most min_slots slots is one item, which writes the block's packed entries
-        // itself (slot size | kItemSingle): no item hand-off level (config4: every block, k_schur
-        // 9.2 -> 8.7 us).  Larger blocks keep >= min_slots per item: config5's one block of 250
-        // slots as a single item took 10.7 us against 9.3 as two items and the hand-off.
-        // Blocks of (single_max, min_slots] slots take two items (config5's 250-slot block: k_schur
-        // 10.5 us as one item vs 9.8 as two under rocprofv3)
-        const int nsl = end - begin, single_max = std::min(min_slots, 160);
-        int per_item = std::max(min_slots, (nsl + 23) / 24);
-        if (nsl > single_max && nsl <= per_item) per_item = (nsl + 1) / 2;
-        const int single = (nsl <= per_item) ? mcc::kItemSingle : 0;
-        for (int s = begin; s < end; s += per_item) {
-            items.push_back(make_int4(b, (int)(base + (size_t)(s - begin) * stride), std::min(end, s + per_item) - s,
-                                      stride | single));
-            p->max_item_slots = std::max(p->max_item_slots, items.back().z);
-        }
-        // a block no photo couples gets one empty item: it writes the block's zeros (every packed
-        // entry is rewritten each step; the all-reduce leaves sums there)
-        if (begin == end) items.push_back(make_int4(b, (int)base, 0, stride | mcc::kItemSingle));
-        block_items[b + 1] = (int)items.size();
-    }
-    p->n_pair_doubles = n_doubles;
-    // A camera block without an observation here is accepted: a rank of a photo-sharded problem
-    // may hold no photo of some camera while the summed system is fine.  If the whole problem
-    // leaves a camera unobserved, the reduced system is singular and the step fails with
-    // MCC_ENOTPD (the device positive-definiteness check of the solve).
-    p->n_items = (int)items.size();
-    p->n_pairs = n_slots;
-    p->n_norm_chunks = (V + 255) / 256;
-    // one hand-off level (m <= 30) while the final arriver loads everything in one batch
-    const bool one_fits = p->m <= 30 && 48 * (p->n_items + p->n_norm_chunks) + p->m * p->m <= mcc::kSchurOneLevelLoads * 256;
-    p->schur_one_level = one_fits ? 1 : 0;
-    if (const char* f = std::getenv("MCC_SCHUR_ONE_LEVEL")) p->schur_one_level = one_fits && std::atoi(f) != 0;
-    if (p->m > 128) return bail(fail(MCC_EINVAL, "global block larger than 128 parameters (22 cameras)"));
-    p->group_size = std::max(1, (int)std::ceil(std::sqrt((double)std::max(V, 1))));
-    p->n_groups = (std::max(V, 1) + p->group_size - 1) / p->group_size;
-
-    // ---- fixed transforms
-    std::vector<float> cam_rt(6 * C, 0.f);
-    if (d->model == MCC_MODEL_DOUBLESIDE) {
-        for (int c = 0; c < C; ++c) {
-            double R[9], r[3];
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) R[i * 3 + j] = d->cam_pose[16 * c + i * 4 + j];
-            host_rodrigues_m2v(R, r);
-            for (int i = 0; i < 3; ++i) { cam_rt[6 * c + i] = (float)r[i]; cam_rt[6 * c + 3 + i] = d->cam_pose[16 * c + i * 4 + 3]; }
-        }
-    }
-    double ds_rt[6] = {0, 0, 0, 0, 0, 0};
-    if (d->ds_pose && d->model == MCC_MODEL_PINHOLE) {
-        double R[9];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) R[i * 3 + j] = d->ds_pose[i * 4 + j];
-        host_rodrigues_m2v(R, ds_rt);
-        for (int i = 0; i < 3; ++i) ds_rt[3 + i] = d->ds_pose[i * 4 + 3];
-    }
-    std::vector<double> alpha(4096);
-    for (size_t k = 0; k < alpha.size(); ++k) alpha[k] = std::pow(0.95, (double)k + 1.0);   // src/multicalib.cpp:483
-
-    // ---- uploads
-    HIPC(p->obj_x.upload(ox.data(), ncorner)); HIPC(p->obj_y.upload(oy.data(), ncorner));
-    HIPC(p->obj_z.upload(oz.data(), ncorner));
-    HIPC(p->img_u.upload(iu.data(), ncorner)); HIPC(p->img_v.upload(iv.data(), ncorner));
-    HIPC(p->edge_info.upload(info.data(), E));
-    HIPC(p->edge_gblock.upload(gblock.data(), E));
-    HIPC(p->edge_photo.upload(ephoto.data(), E));
-    HIPC(p->photo_ptr.upload(photo_ptr.data(), V + 1));
-    HIPC(p->photo_corner.upload(photo_corner.data(), V + 1));
-    HIPC(p->K.upload(d->K, 9 * C));
+    HIPC(p->gpair_ptr.upload(plan.gpair_ptr));
+    HIPC(p->gpairs.upload(plan.gpairs));
+    HIPC(p->gcon_ptr.upload(plan.gcon_ptr));
+    HIPC(p->gcon.upload(plan.gcon));
+    HIPC(p->items.upload(plan.items));
+    HIPC(p->block_items.upload(plan.block_items));
+    // ---- the descriptor's intrinsics
+    HIPC(p->K.upload(d->K, 9 * (size_t)C));
     HIPC(p->D.upload(d->D, (size_t)d->nd * C));
     std::vector<float> xi(C, 0.f);
     if (d->xi) std::copy(d->xi, d->xi + C, xi.begin());
-    HIPC(p->xi.upload(xi.data(), C));
-    HIPC(p->cam_rt.upload(cam_rt.data(), 6 * C));
-    std::vector<float> cp(16 * C, 0.f);
-    if (d->cam_pose) std::copy(d->cam_pose, d->cam_pose + 16 * C, cp.begin());
-    HIPC(p->cam_pose.upload(cp.data(), 16 * C));
-    HIPC(p->ds_rt.upload(ds_rt, 6));
-    HIPC(p->alpha.upload(alpha.data(), alpha.size()));
-    HIPC(p->pgrp_ptr.upload(pgrp_ptr.data(), pgrp_ptr.size()));
-    {
-        std::vector<int> pgrp_edge(pgrp_ptr.size());
-        for (size_t g = 0; g < pgrp_ptr.size(); ++g) pgrp_edge[g] = photo_ptr[pgrp_ptr[g]];
-        HIPC(p->pgrp_edge.upload(pgrp_edge.data(), pgrp_edge.size()));
-        std::vector<unsigned char> lph(std::max(E, 1), 0);
-        for (size_t g = 0; g + 1 < pgrp_ptr.size(); ++g)
-            for (int v = pgrp_ptr[g]; v < pgrp_ptr[g + 1]; ++v)
-                for (int e = photo_ptr[v]; e < photo_ptr[v + 1]; ++e) lph[e] = (unsigned char)(v - pgrp_ptr[g]);
-        HIPC(p->edge_lphoto.upload(lph.data(), lph.size()));
-        // k_group's per-group headers (kGHdr*, mcc_internal.h): the ranges, the group-relative photo_ptr
-        // entries and the first round's edge records at a fixed stride
-        std::vector<int> hdr((size_t)mcc::kGHdrInts * std::max(NG, 1), 0);
-        for (int g = 0; g < NG; ++g) {
-            int* h = hdr.data() + (size_t)mcc::kGHdrInts * g;
-            const int p0 = pgrp_ptr[g], np = pgrp_ptr[g + 1] - p0, ge0 = photo_ptr[p0], gne = photo_ptr[p0 + np] - ge0;
-            h[0] = p0; h[1] = np; h[2] = ge0; h[3] = gne;
-            h[4] = gpair_ptr[g]; h[5] = gpair_ptr[g + 1] - gpair_ptr[g];
-            h[6] = gcon_ptr[g]; h[7] = gcon_ptr[g + 1] - gcon_ptr[g];
-            for (int q = 0; q <= mcc::kPhotoGroup; ++q) h[mcc::kGHdrPhoto + q] = photo_ptr[p0 + std::min(q, np)] - ge0;
-            for (int le = 0; le < std::min(gne, mcc::kGroupRound); ++le) {
-                const int4 f = info[ge0 + le];
-                int* hi = h + mcc::kGHdrInfo + 4 * le;
-                hi[0] = f.x; hi[1] = f.y; hi[2] = f.z; hi[3] = f.w;
-                h[mcc::kGHdrGb + le] = gblock[ge0 + le];
-                h[mcc::kGHdrEq + le] = lph[ge0 + le];
-            }
-        }
-        HIPC(p->ghdr.upload(hdr.data(), hdr.size()));
-        // the cameras' intrinsics rows as k_group keeps them in LDS: fx fy cx cy skew xi k[12] matTilt[9] pad,
-        // each the float's exact value in FP64
-        std::vector<double> kin((size_t)mcc::kGIntr * C, 0.0);
-        for (int c = 0; c < C; ++c) {
-            double* kt = kin.data() + (size_t)mcc::kGIntr * c;
-            const float* Kc = d->K + 9 * c;
-            kt[0] = Kc[0]; kt[1] = Kc[4]; kt[2] = Kc[2]; kt[3] = Kc[5]; kt[4] = Kc[1];
-            kt[5] = d->model == MCC_MODEL_OMNI ? (double)xi[c] : 0.0;
-            for (int q = 0; q < 12; ++q) kt[6 + q] = q < d->nd ? (double)d->D[d->nd * c + q] : 0.0;
-            if (p->prism == 2) tilt_matrix(d->D[14 * c + 12], d->D[14 * c + 13], kt + 18);
-        }
-        HIPC(p->kintr.upload(kin.data(), kin.size()));
-    }
-    if (!p->fused && !p->use_group) {
-        // k_prep4's groups: consecutive photos, <= kPrepPhotos of them and kPrepEdges edges (or one photo)
-        if (const char* f = std::getenv("MCC_PREP_LANES")) p->prep_lanes = std::atoi(f) == 4 ? 4 : 1;
-        std::vector<int> pp(1, 0);
-        for (int v = 0; v < V;) {
-            int w = v, edges = 0;
-            while (w < V && w - v < mcc::kPrepPhotos &&
-                   (w == v || edges + (photo_ptr[w + 1] - photo_ptr[w]) <= mcc::kPrepEdges)) {
-                edges += photo_ptr[w + 1] - photo_ptr[w];
-                ++w;
-            }
-            pp.push_back(w);
-            v = w;
-        }
-        std::vector<int> pe(pp.size());
-        for (size_t g = 0; g < pp.size(); ++g) pe[g] = photo_ptr[pp[g]];
-        p->n_prep = (int)pp.size() - 1;
-        HIPC(p->prep_ptr.upload(pp.data(), pp.size()));
-        HIPC(p->prep_edge.upload(pe.data(), pe.size()));
-    }
-    HIPC(p->gpair_ptr.upload(gpair_ptr.data(), gpair_ptr.size()));
-    HIPC(p->gpairs.upload(gpairs.data(), gpairs.size()));
-    HIPC(p->gcon_ptr.upload(gcon_ptr.data(), gcon_ptr.size()));
-    HIPC(p->gcon.upload(gcon.data(), gcon.size()));
-    HIPC(p->items.upload(items.data(), items.size()));
-    HIPC(p->block_items.upload(block_items.data(), block_items.size()));
+    HIPC(p->xi.upload(xi));
+    std::vector<float> cp(16 * (size_t)C, 0.f);
+    if (d->cam_pose) std::copy(d->cam_pose, d->cam_pose + 16 * (size_t)C, cp.begin());
+    HIPC(p->cam_pose.upload(cp));
+
+    // ---- the step's working buffers
     HIPC(p->x.alloc(p->P)); HIPC(p->xerr.alloc(p->P));
     HIPC(p->Y.alloc(36 * (size_t)E));
     HIPC(p->pairprod.alloc(p->fused ? 0 : p->n_pair_doubles));
@@ -1167,14 +720,12 @@ int mcc_create(mcc_problem** out, const mcc_desc* d) {
     HIPC(p->zp.alloc(6 * (size_t)V));
     HIPC(p->gp_tot.alloc(6 * (size_t)V));
     // + 24 zeroed items of padding: the assembly loads a fixed 24 items per block unconditionally
-    HIPC(p->item_out.alloc(48 * (size_t)(items.size() + p->n_norm_chunks + 24)));
+    HIPC(p->item_out.alloc(48 * (size_t)(p->n_items + p->n_norm_chunks + 24)));
     HIPC(hipMemset(p->item_out.p, 0, sizeof(double) * p->item_out.n));
     HIPC(p->counter.alloc(1));
     HIPC(hipMemset(p->counter.p, 0, sizeof(int)));
     HIPC(p->cnt_blk.alloc(p->nblk));
     HIPC(hipMemset(p->cnt_blk.p, 0, sizeof(int) * std::max(p->nblk, 1)));
-    p->ntri = p->m * (p->m + 1) / 2;
-    p->packed_len = p->ntri + 2 * p->m + 2;
     HIPC(p->packed.alloc(p->packed_len));
     HIPC(p->dg.alloc(p->m)); HIPC(p->delta.alloc(p->P));
     HIPC(p->photo_norm.alloc(2 * (size_t)V));
@@ -1194,110 +745,27 @@ int mcc_create(mcc_problem** out, const mcc_desc* d) {
     std::memset(p->h_state, 0, sizeof(State));
     p->h_state->change = 1.0;
     HIPC(hipMemcpy(p->state.p, p->h_state, sizeof(State), hipMemcpyHostToDevice));
-    if (C > 63) return bail(fail(MCC_EINVAL, "more than 63 cameras"));
-    if (p->fused && mcc_lin_shmem(p->max_epp, C, p->m, p->max_cpp) > 160 * 1024)
-        return bail(fail(MCC_EINVAL, "too many edges / corners per photo for the LDS staging"));
-    if (!p->fused && !p->use_group && p->photo_shmem > 160 * 1024)
-        return bail(fail(MCC_EINVAL, "too many Schur pairs of one photo for k_photo's LDS"));
-    if (!p->fused && p->use_group && p->group_shmem > 160 * 1024)
-        return bail(fail(MCC_EINVAL, "too many edges / Schur pairs of one photo group for k_group's LDS"));
-    HIPC(mcc_set_kernel_attrs(p->max_epp, C, p->m, p->max_cpp, p->photo_shmem, p->use_group ? p->group_shmem : 0));
-    // m <= 30 on k_group -> k_schur (config4): the previous system's inverse from a spare k_group
-    // workgroup, refinement in k_schur's final solve (MCC_SMALL_WARM=0: the register Gauss-Jordan
-    // only).  With S and the inverse in registers the refinement takes ~1.7 us at m = 18 against the
-    // elimination's ~2.6 (config4, interleaved: 28.9 vs 29.4 us per step); round 4's first form, reading
-    // them from LDS per product, took ~3 us and lost
-    // The fused step (config2) refines with the inverse its previous launch's spare workgroup formed
-    // (two updates stale: the spare and the final arriver of one launch run at the same time); its
-    // LDS holds the spare's [S | I] and the final arriver's S, r and inverse (mcc_lin_shmem).
-    // Two buffers by iteration parity, each tagged with the iteration that made it.
-    {
-        bool sw = (!p->fused && p->use_group && p->schur_one_level &&
-                   p->group_shmem >= (size_t)2 * p->m * p->m * sizeof(double)) ||   // the spare's [S | I] in LDS
-                  (p->fused && p->m <= 30);
-        if (const char* f = std::getenv("MCC_SMALL_WARM")) sw = sw && std::atoi(f) != 0;
-        if (sw) {
-            HIPC(p->ssinv.alloc(2 * (size_t)p->m * p->m));
-            HIPC(p->ssinv_ok.alloc(2));
-            HIPC(hipMemset(p->ssinv_ok.p, 0, 2 * sizeof(int)));
-            HIPC(p->warm_stats.alloc(5));   // mcc_solve_stats
-            HIPC(hipMemset(p->warm_stats.p, 0, 5 * sizeof(long long)));
-        }
+    if (p->small_warm) {   // two inverse buffers by iteration parity, each tagged with the iteration that made it
+        HIPC(p->ssinv.alloc(2 * (size_t)p->m * p->m));
+        HIPC(p->ssinv_ok.alloc(2));
+        HIPC(hipMemset(p->ssinv_ok.p, 0, 2 * sizeof(int)));
+        HIPC(p->warm_stats.alloc(5));   // mcc_solve_stats
+        HIPC(hipMemset(p->warm_stats.p, 0, 5 * sizeof(long long)));
     }
-    // the folded reduction: k_group's one-level m <= 30 step with items of at most kSub x kFoldSlots
-    // slots (every m <= 30 rig with several camera-pair blocks takes 64; a one-block rig 320: no fold)
-    p->gfold = !p->fused && p->use_group && p->schur_one_level && p->max_item_slots <= 5 * 13 &&
-               48 * (p->n_items + p->n_norm_chunks) + p->m * p->m + 1 <= mcc::kSchurOneLevelLoads * 256;
-    // Progress of the folded launch does not rest on dispatch order.  Its producers (the groups, the
-    // spare) never wait; its consumers (items, norm chunks, the final workgroup) spin until their words
-    // land.  Whatever order the dispatcher picks, the launch completes as long as the spinning
-    // consumers cannot hold every workgroup slot a producer needs: with at least one slot left over,
-    // some producer is always resident or dispatchable, runs to its end and frees its slot.  k_group
-    // fits at least one workgroup per CU, so the fold is taken only when the consumers fill at most
-    // half of the CUs (the other half stays for producers even when another kernel shares the device);
-    // otherwise the step is k_group -> k_schur.  MCC_FOLD_CONSUMERS_FIRST=1 (tests) lays the grid out
-    // with the consumers at the lowest indices to exercise exactly that.
-    const int fold_spin = p->n_items + p->n_norm_chunks + 1;
-    p->gfold = p->gfold && 2 * fold_spin <= n_cu_dev;
-    if (const char* f = std::getenv("MCC_GFOLD")) p->gfold = p->gfold && std::atoi(f) != 0;
-    if (const char* f = std::getenv("MCC_FOLD_CONSUMERS_FIRST"))   // (a test instantiation, omnidir rigs)
-        p->fold_first = p->gfold && p->model == MCC_MODEL_OMNI && std::atoi(f) != 0;
     if (p->gfold) {
-        // the final workgroup's LDS (k_schur's one-level layout) within k_group's
-        const size_t fs = mcc::schur_lds_bytes(p->m, 1, 1, 1, p->n_items + p->n_norm_chunks, p->nblk);
-        if (fs > p->group_shmem) {
-            p->group_shmem = fs;
-            HIPC(mcc_set_kernel_attrs(p->max_epp, C, p->m, p->max_cpp, p->photo_shmem, p->group_shmem));
-        }
         HIPC(p->fnorm.alloc(4 * (size_t)std::max(V, 1)));
         HIPC(p->fiv.alloc((size_t)p->m * p->m + 1));
-        int max_bi = 0;
-        for (int b = 0; b < p->nblk; ++b) max_bi = std::max(max_bi, block_items[b + 1] - block_items[b]);
-        const int ivt = 512 - 48 * p->nblk - 2;   // the inverse's threads
-        p->fold_direct = p->group_lanes == 32 && max_bi <= 8 && p->n_norm_chunks <= 4 && ivt > 0 &&
-                         p->m * p->m <= 8 * ivt;
-        if (const char* f = std::getenv("MCC_FOLD_DIRECT")) p->fold_direct = p->fold_direct && std::atoi(f) != 0;
-        // MCC_FOLD_DYN=1: the groups themselves take the items, norm chunks and the final task by ticket
-        // once their own work is done, instead of trailing workgroups that wait for a CU the groups free
-        // (config5's 500-view shard: the trailing items started 1.5 us after the last group ended).
-        // Measured, not the default: config4 26.55 vs 26.41 us per step, config5's shard 29.3 vs 29.5
-        // (interleaved, gpurun_out/r05u) -- the last group's slots, not the items' start, set the tail.
-        // With fold_dyn a finished group spins on slots of groups that may not have started, so the
-        // whole grid must be resident at once: the groups and the spare within one workgroup per CU.
-        const char* fd = std::getenv("MCC_FOLD_DYN");
-        p->fold_dyn = fd && std::atoi(fd) != 0 && p->n_pgroups >= 2 * (p->n_items + p->n_norm_chunks + 1) &&
-                      p->prism != 2 && p->n_pgroups + 1 <= n_cu_dev;
         if (p->fold_dyn) {
             HIPC(p->fold_ticket.alloc(1));
             HIPC(hipMemset(p->fold_ticket.p, 0, sizeof(int)));
         }
+        // the fold's hand-off words are their own flags: kFoldEmpty between launches
         for (auto* b : {&p->pairprod, &p->item_out, &p->fnorm, &p->fiv})
             if (b->p) HIPC(hipMemset(b->p, 0xFF, sizeof(double) * std::max<size_t>(b->n, 1)));
     }
-    p->warm = !p->fused && p->m > 30;
-    if (const char* f = std::getenv("MCC_WARM")) p->warm = p->warm && std::atoi(f) != 0;
-    p->helper_refine = p->warm && p->m <= 96;   // (single GPU only: warm_ctx, enqueue_step; the warm path's M <= 96)
-    if (const char* f = std::getenv("MCC_HELPER_REFINE")) p->helper_refine = p->helper_refine && std::atoi(f) != 0;
-    p->helper_early = p->helper_refine && !p->use_group;
-    if (const char* f = std::getenv("MCC_HELPER_POLL")) p->helper_early = p->helper_refine && std::atoi(f) != 0;
-    p->inv_la = p->use_group;   // (mcc_kernels.hip gj_inverse_blocked: where the helper's cycle bounds the step)
-    if (const char* f = std::getenv("MCC_INV_LA")) p->inv_la = std::atoi(f) != 0;
-    if (const char* f = std::getenv("MCC_WARM_POISON")) p->warm_poison = std::atoi(f);
-    if (const char* f = std::getenv("MCC_WARM_TIMEOUT_MS")) p->warm_wait_ticks = (long long)(std::max(1.0, std::atof(f)) * 1e5);
-    if (const char* f = std::getenv("MCC_WARM_DELAY_US")) p->warm_delay_ticks = (long long)(std::max(0.0, std::atof(f)) * 1e2);
-    if (const char* f = std::getenv("MCC_SPARE_DELAY_US")) p->spare_delay_ticks = (long long)(std::max(0.0, std::atof(f)) * 1e2);
-    if (const char* f = std::getenv("MCC_SOLVE_STATS")) p->small_stats = std::atoi(f) != 0;
-    if (const char* f = std::getenv("MCC_FAULT_PHOTO")) p->fault_photo = std::atoi(f);
-    {
-        double peer_ms = 30000.0;   // the helper outlives a k_solve's longest wait at a peer exchange
-        if (const char* t = std::getenv("MCC_PEER_TIMEOUT_MS")) peer_ms = std::max(1.0, std::atof(t));
-        p->warm_idle_ticks = p->warm_wait_ticks + (long long)(peer_ms * 1e5) + 100000000LL;
-    }
-    p->warm = p->warm && p->m <= 96;   // the staged system and inverse fit k_solve's LDS up to M = 96
     if (p->warm) {
         const size_t M = 16 * (size_t)((p->m + 15) / 16);
         HIPC(hipMalloc((void**)&p->sinv, M * M * sizeof(double)));   // cached: the helper releases it, k_solve reads it in a later launch
-        p->prev_stride = (p->ntri + p->m + 1) & ~1;
         HIPC(hipExtMallocWithFlags((void**)&p->prev2, 2 * (size_t)p->prev_stride * sizeof(double), hipDeviceMallocUncached));
         if (int r = reset_prev2(p, true)) return bail(r);
         HIPC(hipExtMallocWithFlags((void**)&p->wsync, 8 * sizeof(unsigned), hipDeviceMallocUncached));
@@ -1308,8 +776,8 @@ int mcc_create(mcc_problem** out, const mcc_desc* d) {
         HIPC(hipMemset(p->warm_stats.p, 0, 5 * sizeof(long long)));
         HIPC(stream_pool().take(d->device, &p->side, true));
     }
+    HIPC(mcc_set_kernel_attrs(p->max_epp, C, p->m, p->max_cpp, p->photo_shmem, p->use_group ? p->group_shmem : 0));
 #undef HIPC
-    (void)rc;
     *out = p;
     return MCC_OK;
 }
@@ -1950,9 +1418,6 @@ int mcc_peer_init(mcc_problem* p, const unsigned char* handles, int nranks, int 
     }
     if (!p->peers_dev) HIPCHK(hipMalloc((void**)&p->peers_dev, mcc_problem::kPeerMaxRanks * sizeof(void*)));
     HIPCHK(hipMemcpy(p->peers_dev, ptrs.data(), nranks * sizeof(void*), hipMemcpyHostToDevice));
-    double ms = 30000.0;
-    if (const char* t = std::getenv("MCC_PEER_TIMEOUT_MS")) ms = std::max(1.0, std::atof(t));
-    p->peer_timeout = (long long)(ms * 1e5);   // s_memrealtime: 100 MHz
     p->peer_n = nranks;
     p->rank = rank;
     p->nranks = nranks;
