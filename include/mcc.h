@@ -281,6 +281,66 @@ typedef struct mcc_pnp_desc {
 int mcc_solve_pnp_batch(const mcc_pnp_desc *d, double *rvec, double *tvec, double *rms, int *status,
                         double *device_ms);
 
+/* ---- pinhole intrinsics: cv::calibrateCamera for one camera.  The returned K, D and view poses are
+ * the least-squares minimum of the reprojection error through cv::projectPoints' model (k1 k2 p1 p2
+ * [k3 [k4 k5 k6]]; no thin-prism or tilt terms), found by Levenberg-Marquardt on the device: one
+ * wavefront per view, the block-arrow elimination per trial, sums in view order (two calls give the
+ * same bits).  Bit parity with OpenCV is not claimed.  Flags carry cv::CALIB_*'s values; any other bit
+ * is MCC_EINVAL. */
+#define MCC_CALIB_USE_INTRINSIC_GUESS 1
+#define MCC_CALIB_FIX_ASPECT_RATIO 2      /* fx = a fy with a = fx / fy of the input K; only fy is free */
+#define MCC_CALIB_FIX_PRINCIPAL_POINT 4
+#define MCC_CALIB_ZERO_TANGENT_DIST 8     /* p1 = p2 = 0, fixed */
+#define MCC_CALIB_FIX_FOCAL_LENGTH 16
+#define MCC_CALIB_FIX_K1 32
+#define MCC_CALIB_FIX_K2 64
+#define MCC_CALIB_FIX_K3 128
+#define MCC_CALIB_FIX_K4 2048
+#define MCC_CALIB_FIX_K5 4096
+#define MCC_CALIB_FIX_K6 8192
+#define MCC_CALIB_RATIONAL_MODEL 16384    /* k4 k5 k6 are free (nd = 8); without it they keep their input values */
+
+#define MCC_CALIB_CONVERGED 0   /* |x_new - x_old| / |x_old| < eps after an accepted step          */
+#define MCC_CALIB_COUNT 1       /* max_count accepted steps                                         */
+#define MCC_CALIB_STALLED 2     /* ten rejected trials in a row; the best parameters are returned   */
+
+typedef struct mcc_calib_desc {
+    int n_views;
+    const int *view_off;     /* [n_views+1] corner offsets; 4 to 1024 corners per view */
+    const double *obj;       /* [3*corners] object points                              */
+    const double *img;       /* [2*corners] observed corners (pixels)                  */
+    int image_width, image_height;
+    int flags;               /* MCC_CALIB_*                                            */
+    int nd;                  /* 4, 5 or 8 distortion coefficients (4: k3 stays 0)      */
+    int crit_type;           /* MCC_CRIT_*; cv::calibrateCamera's default is COUNT_EPS, 30, DBL_EPSILON */
+    int max_count;           /* accepted steps at most (MCC_CRIT_EPS alone: 1000)      */
+    double eps;
+    int device;
+    int *trials;             /* out, may be NULL: trials run (one k_pc_lin + k_pc_try pair each, accepted or not) */
+} mcc_calib_desc;
+
+/* The 0/1 mask of free slots over fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 that flags and nd give (under
+ * FIX_ASPECT_RATIO fx is 0: it follows fy).  MCC_EINVAL for an unknown flag bit or a bad nd. */
+int mcc_calib_mask(int flags, int nd, int *mask /* [12] */);
+
+/* cv::initCameraMatrix2D: the closed-form K (Zhang's constraints on every view's homography, principal
+ * point at the image centre) for planar targets; host only.  aspect_ratio > 0 forces fx = aspect_ratio fy,
+ * 0 leaves both free.  Uses n_views, view_off, obj, img and the image size of the descriptor.  MCC_EINVAL
+ * when an object point has Z != 0; MCC_ENOTPD when the views do not determine the focal lengths. */
+int mcc_init_camera_matrix(const mcc_calib_desc *d, double aspect_ratio, double *K /* [9] */);
+
+/* K[9] and D[nd] are in/out: the start with USE_INTRINSIC_GUESS (which a non-planar target requires),
+ * otherwise only the aspect ratio under FIX_ASPECT_RATIO is read from them and the start is
+ * mcc_init_camera_matrix's K with zero distortion (a fixed slot then stays at that start).  The pose seeds are one internal mcc_solve_pnp_batch.  rvec[3*n_views], tvec[3*n_views],
+ * view_rms[n_views] (each view's RMS over its corners), rms = sqrt(sum |e|^2 / corners), iterations
+ * (accepted steps), status (MCC_CALIB_*) and device_ms (HIP events around the whole loop, the host's reads of
+ * the loop state between batches of trials included) may each be NULL.
+ * MCC_EINVAL, before any device work, for a null pointer, n_views <= 0, a view_off that decreases, a view
+ * of fewer than 4 or more than 1024 corners, a bad nd, an unknown flag bit, a zero focal length under
+ * FIX_ASPECT_RATIO, or Z != 0 without a guess. */
+int mcc_calibrate_camera(const mcc_calib_desc *d, double *K, double *D, double *rvec, double *tvec,
+                         double *view_rms, double *rms, int *iterations, int *status, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,75 @@
+/*
+ * mcc_calib.hpp -- cv::calibrateCamera and cv::initCameraMatrix2D for one pinhole camera, over
+ * mcc_calibrate_camera / mcc_init_camera_matrix (include/mcc.h, libmcc.so); implemented in libmcc_host.so
+ * (host/calib.cpp).  Argument order and return value follow
+ *
+ *   double calibrateCamera(InputArrayOfArrays objectPoints, InputArrayOfArrays imagePoints, Size imageSize,
+ *                          InputOutputArray cameraMatrix, InputOutputArray distCoeffs, OutputArrayOfArrays rvecs,
+ *                          OutputArrayOfArrays tvecs, int flags = 0,
+ *                          TermCriteria criteria = TermCriteria(COUNT + EPS, 30, DBL_EPSILON));
+ *   Mat initCameraMatrix2D(InputArrayOfArrays objectPoints, InputArrayOfArrays imagePoints, Size imageSize,
+ *                          double aspectRatio = 1.0);
+ *
+ * The result is the least-squares minimum of the reprojection error through cv::projectPoints' model, found by
+ * Levenberg-Marquardt on the GPU; bit parity with OpenCV is not claimed.  distCoeffs has 8 entries
+ * with CALIB_RATIONAL_MODEL and 5 otherwise (a vector handed in with another size is resized; its leading entries
+ * are the guess under CALIB_USE_INTRINSIC_GUESS).  Thin-prism and tilted-sensor flags throw.
+ */
+#ifndef MCC_CALIB_HPP
+#define MCC_CALIB_HPP
+
+#include <array>
+#include <cfloat>
+#include <vector>
+
+#include "mcc.h"
+#include "mcc_multicalib.hpp"
+
+namespace mcc {
+namespace calib {
+
+enum {
+    CALIB_USE_INTRINSIC_GUESS = MCC_CALIB_USE_INTRINSIC_GUESS,
+    CALIB_FIX_ASPECT_RATIO = MCC_CALIB_FIX_ASPECT_RATIO,
+    CALIB_FIX_PRINCIPAL_POINT = MCC_CALIB_FIX_PRINCIPAL_POINT,
+    CALIB_ZERO_TANGENT_DIST = MCC_CALIB_ZERO_TANGENT_DIST,
+    CALIB_FIX_FOCAL_LENGTH = MCC_CALIB_FIX_FOCAL_LENGTH,
+    CALIB_FIX_K1 = MCC_CALIB_FIX_K1,
+    CALIB_FIX_K2 = MCC_CALIB_FIX_K2,
+    CALIB_FIX_K3 = MCC_CALIB_FIX_K3,
+    CALIB_FIX_K4 = MCC_CALIB_FIX_K4,
+    CALIB_FIX_K5 = MCC_CALIB_FIX_K5,
+    CALIB_FIX_K6 = MCC_CALIB_FIX_K6,
+    CALIB_RATIONAL_MODEL = MCC_CALIB_RATIONAL_MODEL
+};
+
+using Vec3d = std::array<double, 3>;
+using Vec2d = std::array<double, 2>;
+using Size = multicalib::Size;
+using TermCriteria = multicalib::TermCriteria;
+
+// what cv::calibrateCamera does not return: the loop's end (MCC_CALIB_*), accepted steps, per-view RMS, device time
+struct CalibInfo {
+    int status = 0, iterations = 0, trials = 0;
+    std::vector<double> viewRms;
+    double deviceMs = 0;
+};
+
+// Throws std::invalid_argument for mismatched point lists and std::runtime_error with the library's message
+// when the call fails (a bad argument, a view without a pose seed, no GPU).
+double calibrateCamera(const std::vector<std::vector<Vec3d>>& objectPoints,
+                       const std::vector<std::vector<Vec2d>>& imagePoints, Size imageSize,
+                       std::array<double, 9>& cameraMatrix, std::vector<double>& distCoeffs, std::vector<Vec3d>& rvecs,
+                       std::vector<Vec3d>& tvecs, int flags = 0,
+                       TermCriteria criteria = TermCriteria(TermCriteria::COUNT + TermCriteria::EPS, 30, DBL_EPSILON),
+                       CalibInfo* info = nullptr, int device = 0);
+
+// aspectRatio = 0 leaves fx and fy free; OpenCV's default of 1 forces fx = fy.  Host only.
+std::array<double, 9> initCameraMatrix2D(const std::vector<std::vector<Vec3d>>& objectPoints,
+                                         const std::vector<std::vector<Vec2d>>& imagePoints, Size imageSize,
+                                         double aspectRatio = 1.0);
+
+}  // namespace calib
+}  // namespace mcc
+
+#endif

@@ -350,8 +350,9 @@ public:
     // file (an image name maps to <stem>.yaml beside it) holding imagePoints (N x 2 or N x 1 x 2),
     // objectPoints (N x 3 or N x 1 x 3) and imageSize; views with more than nMiniMatches points are
     // kept; OMNIDIRECTIONAL cameras are calibrated with cv::omnidir::calibrate on the GPU
-    // (mcc_omnidir.hpp, TermCriteria(COUNT + EPS, 300, 1e-7), flags), PINHOLE would need
-    // cv::calibrateCamera (not restated: throws); the calibration's view poses become the edges
+    // (mcc_omnidir.hpp, TermCriteria(COUNT + EPS, 300, 1e-7), flags), PINHOLE cameras with
+    // cv::calibrateCamera on the GPU (mcc_calib.hpp, flags, its default criteria; five distortion
+    // coefficients, eight with CALIB_RATIONAL_MODEL); the calibration's view poses become the edges
     virtual void loadImages();
     // readStringList (src/multicalib.cpp:167-180): the strings of the list file's first node
     std::vector<std::string> readStringList() const;

@@ -82,6 +82,20 @@ class _PnpDesc(ctypes.Structure):
 
 PNP_SOLVED, PNP_TOO_FEW, PNP_DEGENERATE = 0, 1, 2
 
+
+class _CalibDesc(ctypes.Structure):
+    _fields_ = [("n_views", ctypes.c_int), ("view_off", _i32p), ("obj", _f64p), ("img", _f64p),
+                ("image_width", ctypes.c_int), ("image_height", ctypes.c_int), ("flags", ctypes.c_int),
+                ("nd", ctypes.c_int), ("crit_type", ctypes.c_int), ("max_count", ctypes.c_int), ("eps", ctypes.c_double),
+                ("device", ctypes.c_int), ("trials", _i32p)]
+
+
+# cv::CALIB_* values (include/mcc.h: MCC_CALIB_*)
+CV_CALIB_USE_INTRINSIC_GUESS, CV_CALIB_FIX_ASPECT_RATIO, CV_CALIB_FIX_PRINCIPAL_POINT, CV_CALIB_ZERO_TANGENT_DIST = 1, 2, 4, 8
+CV_CALIB_FIX_FOCAL_LENGTH, CV_CALIB_FIX_K1, CV_CALIB_FIX_K2, CV_CALIB_FIX_K3 = 16, 32, 64, 128
+CV_CALIB_FIX_K4, CV_CALIB_FIX_K5, CV_CALIB_FIX_K6, CV_CALIB_RATIONAL_MODEL = 2048, 4096, 8192, 16384
+CALIB_CONVERGED, CALIB_COUNT, CALIB_STALLED = 0, 1, 2
+
 _LIB = None
 
 
@@ -218,7 +232,11 @@ def lib():
                                                                                              ctypes.c_int, _f32p, _u8p, _ll,
                                                                                              _u8p, _ll, _f32p, _ll,
                                                                                              ctypes.POINTER(_ll)]),
-                ("mcc_solve_pnp_batch", [ctypes.POINTER(_PnpDesc), _f64p, _f64p, _f64p, _i32p, _f64p])):
+                ("mcc_solve_pnp_batch", [ctypes.POINTER(_PnpDesc), _f64p, _f64p, _f64p, _i32p, _f64p]),
+                ("mcc_calib_mask", [ctypes.c_int, ctypes.c_int, _i32p]),
+                ("mcc_init_camera_matrix", [ctypes.POINTER(_CalibDesc), ctypes.c_double, _f64p]),
+                ("mcc_calibrate_camera", [ctypes.POINTER(_CalibDesc), _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p,
+                                          _i32p, _f64p])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
         for name in ("mcc_omnirect_destroy", "mcc_omnirecon_destroy"):
@@ -293,6 +311,61 @@ def solve_pnp(obj, img, off, K, D, view_cam=None, max_iter=50, device=0, return_
                                      _ptr(status, _i32p), _ptr(ms, _f64p)), "mcc_solve_pnp_batch")
     out = (rvec, tvec, rms, status)
     return out + (float(ms[0]),) if return_ms else out
+
+
+def calib_mask(flags=0, nd=5):
+    """The 0/1 mask of free slots over fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 that cv::calibrateCamera's flags
+    and the distortion width nd give (mcc_calib_mask)."""
+    m = np.zeros(12, np.int32)
+    _check(lib().mcc_calib_mask(int(flags), int(nd), _ptr(m, _i32p)), "mcc_calib_mask")
+    return m
+
+
+def _calib_desc(off, obj, img, image_size, flags, nd, crit_type, max_count, eps, device):
+    off = np.ascontiguousarray(off, np.int32).reshape(-1)
+    obj = np.ascontiguousarray(obj, np.float64).reshape(-1, 3)
+    img = np.ascontiguousarray(img, np.float64).reshape(-1, 2)
+    n_views = len(off) - 1
+    if n_views >= 1 and (len(obj) < off[-1] or len(img) < off[-1]):
+        raise MccError(f"calibrate_camera: off names {off[-1]} corners, obj has {len(obj)} and img {len(img)}")
+    d = _CalibDesc(n_views, _ptr(off, _i32p), _ptr(obj, _f64p), _ptr(img, _f64p), int(image_size[0]), int(image_size[1]),
+                   int(flags), int(nd), int(crit_type), int(max_count), float(eps), int(device), None)
+    return d, (off, obj, img)   # (the arrays the descriptor points into)
+
+
+def init_camera_matrix(off, obj, img, image_size, aspect_ratio=0.0):
+    """cv::initCameraMatrix2D (mcc_init_camera_matrix): the closed-form K of a planar target's views, image_size
+    = (width, height); aspect_ratio > 0 forces fx = aspect_ratio fy.  Host only."""
+    d, keep = _calib_desc(off, obj, img, image_size, 0, 5, MCC_CRIT_COUNT_EPS, 30, 0.0, 0)
+    K = np.zeros((3, 3))
+    _check(lib().mcc_init_camera_matrix(ctypes.byref(d), float(aspect_ratio), _ptr(K, _f64p)), "mcc_init_camera_matrix")
+    return K
+
+
+def calibrate_camera(off, obj, img, image_size, K=None, D=None, flags=0, nd=5, max_count=30, eps=2.2e-16, device=0,
+                     return_ms=False):
+    """cv::calibrateCamera for one pinhole camera on the GPU (mcc_calibrate_camera): view v owns corners
+    off[v]:off[v + 1] of obj [corners, 3] and img [corners, 2] (pixels); image_size = (width, height); flags are
+    cv::CALIB_*'s (CV_CALIB_* above; the omnidir CALIB_* below are another set); nd in {4, 5, 8}.  K and D are the guess with CV_CALIB_USE_INTRINSIC_GUESS (K also
+    gives the ratio under CV_CALIB_FIX_ASPECT_RATIO).  Returns (rms, K [3, 3], D [nd], rvec [V, 3], tvec [V, 3],
+    view_rms [V], iterations, status): the least-squares minimum of the reprojection error by Levenberg-Marquardt,
+    stopped after max_count accepted steps or a relative step below eps; status CALIB_CONVERGED, CALIB_COUNT or
+    CALIB_STALLED.  With return_ms the loop's device milliseconds and its number of trials are appended."""
+    d, keep = _calib_desc(off, obj, img, image_size, flags, nd, MCC_CRIT_COUNT_EPS, max_count, eps, device)
+    Kio = np.zeros((3, 3)) if K is None else np.array(K, np.float64).reshape(3, 3)
+    Dio = np.zeros(max(int(nd), 1))
+    if D is not None:
+        Din = np.asarray(D, np.float64).reshape(-1)
+        Dio[:min(len(Din), len(Dio))] = Din[:len(Dio)]
+    nv = max(d.n_views, 1)
+    rvec, tvec, vrms = np.zeros((nv, 3)), np.zeros((nv, 3)), np.zeros(nv)
+    rms, ms, it, st, tr = np.zeros(1), np.zeros(1), np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    d.trials = _ptr(tr, _i32p)
+    _check(lib().mcc_calibrate_camera(ctypes.byref(d), _ptr(Kio, _f64p), _ptr(Dio, _f64p), _ptr(rvec, _f64p),
+                                      _ptr(tvec, _f64p), _ptr(vrms, _f64p), _ptr(rms, _f64p), _ptr(it, _i32p),
+                                      _ptr(st, _i32p), _ptr(ms, _f64p)), "mcc_calibrate_camera")
+    out = (float(rms[0]), Kio, Dio[:int(nd)], rvec, tvec, vrms, int(it[0]), int(st[0]))
+    return out + (float(ms[0]), int(tr[0])) if return_ms else out
 
 
 def partition_photos(prob, nranks):

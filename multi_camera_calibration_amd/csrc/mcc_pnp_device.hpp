@@ -145,6 +145,36 @@ MCC_PNP_FN void pnp_rows(const PnpCam& c, const double* R, const double* Jl, con
     }
 }
 
+// The two rows of d pixel / d (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) at the same corner
+// (calibrateCamera's global block, mcc_pincalib_device.hpp; the prism terms are not calibrated).
+MCC_PNP_FN void pnp_rows_intr(const PnpCam& c, const double* R, const double* t, const double* X, double* iu,
+                              double* iv) {
+    const double Xc = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
+    const double Yc = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
+    const double Zc = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+    const double z = Zc != 0.0 ? 1.0 / Zc : 1.0;
+    const double x = Xc * z, y = Yc * z;
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double num = 1 + c.k1 * r2 + c.k2 * r4 + c.k3 * r6, den = 1 + c.k4 * r2 + c.k5 * r4 + c.k6 * r6;
+    const double iden = 1.0 / den, cd = num * iden;
+    const double xd = x * cd + 2 * c.p1 * x * y + c.p2 * (r2 + 2 * x * x) + c.s1 * r2 + c.s2 * r4;
+    const double yd = y * cd + c.p1 * (r2 + 2 * y * y) + 2 * c.p2 * x * y + c.s3 * r2 + c.s4 * r4;
+    const double fxx = c.fx * x * iden, fyy = c.fy * y * iden;   // d (fx xd, fy yd) / d num
+    const double gxx = -fxx * cd, gyy = -fyy * cd;               // ... / d den
+    iu[0] = xd;  iv[0] = 0.0;
+    iu[1] = 0.0; iv[1] = yd;
+    iu[2] = 1.0; iv[2] = 0.0;
+    iu[3] = 0.0; iv[3] = 1.0;
+    iu[4] = fxx * r2; iv[4] = fyy * r2;
+    iu[5] = fxx * r4; iv[5] = fyy * r4;
+    iu[6] = c.fx * (2 * x * y);        iv[6] = c.fy * (r2 + 2 * y * y);
+    iu[7] = c.fx * (r2 + 2 * x * x);   iv[7] = c.fy * (2 * x * y);
+    iu[8] = fxx * r6; iv[8] = fyy * r6;
+    iu[9] = gxx * r2; iv[9] = gyy * r2;
+    iu[10] = gxx * r4; iv[10] = gyy * r4;
+    iu[11] = gxx * r6; iv[11] = gyy * r6;
+}
+
 // ---------------------------------------------------------------- 3 x 3 in registers
 MCC_PNP_FN double pnp_det3(const double* M) {
     return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);

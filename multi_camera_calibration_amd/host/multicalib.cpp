@@ -7,11 +7,13 @@
 //   reset() / run()                 src/multicalib.cpp:127-152
 //   writeParameters(...)            src/multicalib.cpp:1092-1127, src/mymulticalib.cpp:424-456
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <filesystem>
 #include <iostream>
 
+#include "mcc_calib.hpp"
 #include "mcc_multicalib.hpp"
 #include "mcc_omnidir.hpp"
 #include "mcc_pnp.hpp"
@@ -166,20 +168,24 @@ void MultiCameraCalibration::loadImages() {
         if (objs.empty()) throw std::runtime_error("camera " + std::to_string(camera) + " has no usable view");
         if (size.width <= 0 || size.height <= 0)
             throw std::runtime_error("camera " + std::to_string(camera) + ": no imageSize in its corner files");
-        if (_camType != OMNIDIRECTIONAL)
-            throw std::runtime_error(
-                "MultiCameraCalibration::loadImages: PINHOLE intrinsics need cv::calibrateCamera, which is not "
-                "restated here; use MyMultiCameraCalibration with camera configs");
         std::array<double, 9> K{};
-        std::array<double, 4> D{};
-        double xi = 0;
+        std::vector<double> D;
+        double xi = 0, rms = 0;
         std::vector<mcc::omnidir::Vec3d> om, t;
         std::vector<int> idx;
-        const double rms = mcc::omnidir::calibrate(objs, imgs, size, K, xi, D, om, t, _flags,
-                                                   TermCriteria(TermCriteria::COUNT + TermCriteria::EPS, 300, 1e-7),
-                                                   &idx, _device);
+        if (_camType == PINHOLE) {   // cv::calibrateCamera (src/multicalib.cpp:252-262), idx = identity
+            rms = mcc::calib::calibrateCamera(objs, imgs, size, K, D, om, t, _flags,
+                                              TermCriteria(TermCriteria::COUNT + TermCriteria::EPS, 30, DBL_EPSILON),
+                                              nullptr, _device);
+            for (size_t i = 0; i < om.size(); ++i) idx.push_back((int)i);
+        } else {
+            std::array<double, 4> D4{};
+            rms = mcc::omnidir::calibrate(objs, imgs, size, K, xi, D4, om, t, _flags,
+                                          TermCriteria(TermCriteria::COUNT + TermCriteria::EPS, 300, 1e-7), &idx, _device);
+            D.assign(D4.begin(), D4.end());
+        }
         for (int k = 0; k < 9; ++k) _cameraMatrix[camera][k] = (float)K[k];   // convertTo(CV_32F)
-        _distortCoeffs[camera].assign({(float)D[0], (float)D[1], (float)D[2], (float)D[3]});
+        _distortCoeffs[camera].assign(D.begin(), D.end());
         _xi[camera] = (float)xi;
         for (size_t i = 0; i < om.size(); ++i) {   // edges from the calibration's view poses (:296-312)
             const std::array<float, 3> r{(float)om[i][0], (float)om[i][1], (float)om[i][2]};
@@ -192,7 +198,7 @@ void MultiCameraCalibration::loadImages() {
         }
         if (_verbose) {
             std::cout << "initialized for camera " << camera << " rms = " << rms << std::endl;
-            std::cout << "xi for camera " << camera << " is " << _xi[camera] << std::endl;
+            if (_camType == OMNIDIRECTIONAL) std::cout << "xi for camera " << camera << " is " << _xi[camera] << std::endl;
         }
     }
     release();

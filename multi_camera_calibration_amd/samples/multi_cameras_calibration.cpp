@@ -15,9 +15,9 @@
 // --list FILE runs the base MultiCameraCalibration instead, as the reference's multi-camera
 // tutorial does (tutorials/multi_camera_tutorial.markdown: construct, run(), writeParameters):
 // FILE is an imagelist_creator list whose entries after the first are per-view corner files
-// "cameraIdx-timestamp.yaml" (imagePoints, objectPoints, imageSize); with --omni (the only camera
-// type whose intrinsics are restated) every camera is first calibrated by cv::omnidir::calibrate
-// on the GPU.  --cameras N (required), --min-matches K (nMiniMatches, default 20).
+// "cameraIdx-timestamp.yaml" (imagePoints, objectPoints, imageSize); every camera is first
+// calibrated on the GPU, by cv::omnidir::calibrate with --omni and by cv::calibrateCamera (pinhole)
+// without it.  --cameras N (required), --min-matches K (nMiniMatches, default 20).
 //
 // --gpu-pnp seeds every view's pose on the GPU (MyMultiCameraCalibration::gpuPnP: one batched
 // solvePnP launch per loadImages, mcc::pnp::solvePnPBatch) where the default solves view by view on
