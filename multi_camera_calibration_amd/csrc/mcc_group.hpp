@@ -774,25 +774,76 @@ template <int L>
 __device__ __forceinline__ void edge_prio_down() {
     if (L == 32 && MCC_EDGE_PRIO != 0) __builtin_amdgcn_s_setprio(0);
 }
+// A uniform global-memory pointer held in SGPRs from here on (opaque to the compiler, which would
+// otherwise load a kernel argument again where it is used).
+template <class T>
+__device__ __forceinline__ T* pin_global(T* p) {
+    __attribute__((address_space(1))) T* g = (__attribute__((address_space(1))) T*)p;
+    asm volatile("" : "+s"(g));
+    return (T*)g;
+}
+__device__ __forceinline__ int first_lane(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double first_lane(double v) {
+    return __hiloint2double(first_lane(__double2hiint(v)), first_lane(__double2loint(v)));
+}
+// A by-value struct argument of k_group at its byte offset in the argument segment (GroupLead's
+// layout: mcc_internal.h), behind an opaque pointer: its fields are read by scalar loads issued
+// from here on.  Read through the parameter itself, every role's argument loads are hoisted to the
+// kernel's entry, ahead of the role dispatch and each behind a wait of its own, on every role's path.
+template <class T>
+__device__ __forceinline__ const T& kernarg_at(const int off) {
+    typedef const __attribute__((address_space(4))) char* kbytes;
+    const __attribute__((address_space(4))) T* p =
+        (const __attribute__((address_space(4))) T*)((kbytes)__builtin_amdgcn_kernarg_segment_ptr() + off);
+    asm volatile("" : "+s"(p));
+    return *(const T*)p;
+}
+// (the offsets kGArgLin and kGArgHot: computed from the kernel's parameter list, mcc_internal.h)
 // The group's work (phases 0, A, B above); false when the loop has stopped (nothing done).
 template <int MODEL, bool RATIONAL, int PRISM, bool BACK, int L>
-__device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
+__device__ __forceinline__ bool group_body(State* st, const int* __restrict__ ghdr, const bool fold, const int grp,
+                                           const long long t_entry) {
     constexpr int NT = kGroupRound * L, EPW = 64 / L;   // threads; edges per wave
-    State* st = a.state;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wv = __builtin_amdgcn_readfirstlane(wave);   // (uniform: a whole wave's loads are skipped by a scalar branch)
-    // ---- scalar batch: the state and the group's header (the stop test after the loads are issued)
-    const int* __restrict__ hdr = a.ghdr + (size_t)kGHdrInts * grp;
-    const int done = st->done, pending = st->pending;
-    const double alpha_prev = st->alpha;   // step factor of the pending update
-    const int p0 = hdr[kGHdrRange], np = hdr[kGHdrRange + 1];
-    const int ge0 = hdr[kGHdrRange + 2], gne = hdr[kGHdrRange + 3];   // the group's edges are contiguous
-    const int q0 = hdr[kGHdrRange + 4], nq = hdr[kGHdrRange + 5];
-    const int c0 = hdr[kGHdrRange + 6], nc = hdr[kGHdrRange + 7];
+    // ---- scalar batch, ONE round trip: the state words, the group's header ranges and the pointers
+    // phase 0 dereferences (st and ghdr arrive preloaded: no load ahead of these).  The values are
+    // pinned in SGPRs behind the single wait -- left to itself the compiler re-reads an argument where
+    // it is used, each read a wait in front of the next vector load's issue.  The stop test follows.
+    const int* __restrict__ hdr = ghdr + (size_t)kGHdrInts * grp;
+    // (first_lane: a no-op where the load is a scalar one; the tilted sensor's variants get vector loads here)
+    int done = first_lane(st->done), pending = first_lane(st->pending);
+    double alpha_prev = first_lane(st->alpha);   // step factor of the pending update
+    int p0 = first_lane(hdr[kGHdrRange]), np = first_lane(hdr[kGHdrRange + 1]);
+    int ge0 = first_lane(hdr[kGHdrRange + 2]), gne = first_lane(hdr[kGHdrRange + 3]);   // the group's edges are contiguous
+    int q0 = first_lane(hdr[kGHdrRange + 4]), nq = first_lane(hdr[kGHdrRange + 5]);
+    int c0 = first_lane(hdr[kGHdrRange + 6]), nc = first_lane(hdr[kGHdrRange + 7]);
+    GroupHot hp = kernarg_at<GroupHot>(kGArgHot);
+    // (every value in a register at one point: the loads are issued together ahead of it)
+    asm volatile("" ::"s"(done), "s"(pending), "s"(alpha_prev), "s"(p0), "s"(np), "s"(ge0), "s"(gne), "s"(q0), "s"(nq),
+                 "s"(c0), "s"(nc), "s"(hp.gpairs), "s"(hp.gcon), "s"(hp.dg), "s"(hp.kintr), "s"(hp.x), "s"(hp.cam_rt),
+                 "s"(hp.ds_rt), "s"(hp.zp), "s"(hp.photo_norm), "s"(hp.gblock), "s"(hp.Y), "s"(hp.obj_x), "s"(hp.obj_y),
+                 "s"(hp.obj_z), "s"(hp.img_u), "s"(hp.img_v), "s"(hp.stamps), "s"(hp.global_dim), "s"(hp.n_cams));
+    asm volatile("" ::"s"(hp.edge_info), "s"(hp.edge_lphoto), "s"(hp.gp_tot), "s"(hp.resid));
+    asm volatile("" : "+s"(done), "+s"(pending), "+s"(alpha_prev), "+s"(p0), "+s"(np), "+s"(ge0), "+s"(gne), "+s"(q0),
+                 "+s"(nq), "+s"(c0), "+s"(nc), "+s"(hp.global_dim), "+s"(hp.n_cams));
+    // (pinned as global-memory pointers: a generic pointer out of an asm statement makes its loads flat ones)
+    hp.gpairs = pin_global(hp.gpairs); hp.gcon = pin_global(hp.gcon); hp.dg = pin_global(hp.dg);
+    hp.kintr = pin_global(hp.kintr); hp.x = pin_global(hp.x); hp.cam_rt = pin_global(hp.cam_rt);
+    hp.ds_rt = pin_global(hp.ds_rt); hp.zp = pin_global(hp.zp); hp.photo_norm = pin_global(hp.photo_norm);
+    hp.gblock = pin_global(hp.gblock); hp.Y = pin_global(hp.Y); hp.obj_x = pin_global(hp.obj_x);
+    hp.obj_y = pin_global(hp.obj_y); hp.obj_z = pin_global(hp.obj_z); hp.img_u = pin_global(hp.img_u);
+    hp.img_v = pin_global(hp.img_v); hp.stamps = pin_global(hp.stamps);
+    hp.edge_info = pin_global(hp.edge_info); hp.edge_lphoto = pin_global(hp.edge_lphoto);
+    hp.gp_tot = pin_global(hp.gp_tot); hp.resid = pin_global(hp.resid);
     if (done) return false;
-    long long* stp = a.stamps ? a.stamps + kStampStride * (size_t)grp : nullptr;   // MCC_DIAG: slots 0..11
+    long long* stp = hp.stamps ? hp.stamps + kStampStride * (size_t)grp : nullptr;   // MCC_DIAG: slots 0..13
     SSTAMP(stp, 0, 0);
-    const int C = a.n_cams, m = a.global_dim;
+#ifdef MCC_DIAG
+    // the kernel's entry (k_group's first instruction) as wave 0 and the last wave saw it: slots 12, 13
+    if (stp && (tid == 0 || tid == NT - 64)) stp[tid == 0 ? 12 : 13] = t_entry;
+#endif
+    const int C = hp.n_cams, m = hp.global_dim;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const GroupLayout GL = group_layout(gne, C, nq, nc);
 #ifdef MCC_DIAG
@@ -832,11 +883,11 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
         for (int u = 0; u < PER; ++u) {
             const int i = sb + L * u;
             const unsigned c = (unsigned)(eoff + cc0 + (i < cn ? i : 0));
-            v[u][0] = a.obj_x[c];
-            v[u][1] = a.obj_y[c];
-            v[u][2] = a.obj_z[c];
-            v[u][3] = a.img_u[c];
-            v[u][4] = a.img_v[c];
+            v[u][0] = hp.obj_x[c];
+            v[u][1] = hp.obj_y[c];
+            v[u][2] = hp.obj_z[c];
+            v[u][3] = hp.img_u[c];
+            v[u][4] = hp.img_v[c];
         }
     };
     auto stage_store = [&](const float (&v)[PER][5], int sb, int cn) {
@@ -881,22 +932,22 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
     int4 rPq = make_int4(0, 0, 0, 0);
     unsigned rCn = 0;
     double rDg = 0.0, rKt = 0.0;
-    if (wv * 64 < nq) rPq = a.gpairs[q0 + (tid < nq ? tid : 0)];
-    if (wv * 64 < nc) rCn = a.gcon[c0 + (tid < nc ? tid : 0)];
-    if (wv * 64 < m) rDg = a.dg[tid < m ? tid : 0];
-    if (wv * 64 < kGIntr * C) rKt = a.kintr[tid < kGIntr * C ? tid : 0];
+    if (wv * 64 < nq) rPq = hp.gpairs[q0 + (tid < nq ? tid : 0)];
+    if (wv * 64 < nc) rCn = hp.gcon[c0 + (tid < nc ? tid : 0)];
+    if (wv * 64 < m) rDg = hp.dg[tid < m ? tid : 0];
+    if (wv * 64 < kGIntr * C) rKt = hp.kintr[tid < kGIntr * C ? tid : 0];
     // (4) the cameras' poses (lane c of the camera wave) and the double-side transform (its lane 63)
     float rCam[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     double rDs[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (wv == CAM0 / 64) {
         const int c = lane < C ? lane : 0;
-        const float* src = MODEL == MCC_MODEL_DOUBLESIDE ? a.cam_rt + 6 * c : a.x + 6 * (c > 0 ? c - 1 : 0);
-        if (BACK && MODEL == MCC_MODEL_DOUBLESIDE) src = tid == DST ? a.x : src;   // DoubleSide's global block
+        const float* src = MODEL == MCC_MODEL_DOUBLESIDE ? hp.cam_rt + 6 * c : hp.x + 6 * (c > 0 ? c - 1 : 0);
+        if (BACK && MODEL == MCC_MODEL_DOUBLESIDE) src = tid == DST ? hp.x : src;   // DoubleSide's global block
 #pragma unroll
         for (int k = 0; k < 6; ++k) rCam[k] = src[k];
         if (BACK && MODEL != MCC_MODEL_DOUBLESIDE) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) rDs[k] = a.ds_rt[k];
+            for (int k = 0; k < 6; ++k) rDs[k] = hp.ds_rt[k];
         }
     }
     // (5) the pending update's operands: thread (le, k) < 6 gne forms sum_i Y'_e[i][k] dg_g(e)[i]
@@ -909,17 +960,17 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
     double2 pn0 = make_double2(0.0, 0.0);   // the fold without a pending update: the norms k_backsub left
     if (wv == 3) {
         const size_t pi = ptask ? 6 * (size_t)(p0 + pq) + pk : 0;
-        xo = a.x[m + pi];
-        if (pending) zk = a.zp[pi];
-        else if (a.fold) pn0 = *reinterpret_cast<const double2*>(a.photo_norm + (ptask && pk == 0 ? 2 * (size_t)(p0 + pq) : 0));
+        xo = hp.x[m + pi];
+        if (pending) zk = hp.zp[pi];
+        else if (fold) pn0 = *reinterpret_cast<const double2*>(hp.photo_norm + (ptask && pk == 0 ? 2 * (size_t)(p0 + pq) : 0));
     }
     double y0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     int gb0 = -1;
     if (pending && wv * 64 < 6 * gne) {
         const bool act = tid < 6 * gne;
         const int le = act ? tid / 6 : 0, k = act ? tid % 6 : 0;
-        gb0 = a.gblock[ge0 + le];
-        const double* Ye = a.Y + 36 * (size_t)(ge0 + le);
+        gb0 = hp.gblock[ge0 + le];
+        const double* Ye = hp.Y + 36 * (size_t)(ge0 + le);
 #pragma unroll
         for (int i = 0; i < 6; ++i) y0[i] = Ye[6 * i + k];
     }
@@ -967,18 +1018,20 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
     // ---- cold: what one pass per thread does not cover (edges past the header's round, longer lists)
 #pragma unroll 1
     for (int t = kGroupRound + tid; t < gne; t += NT) {
-        sInfo[t] = a.edge_info[ge0 + t];
-        sgb[t] = a.gblock[ge0 + t];
-        seq[t] = a.edge_lphoto[ge0 + t];
+        sInfo[t] = hp.edge_info[ge0 + t];
+        sgb[t] = hp.gblock[ge0 + t];
+        seq[t] = hp.edge_lphoto[ge0 + t];
     }
 #pragma unroll 1
-    for (int t = NT + tid; t < nq; t += NT) spq[t] = a.gpairs[q0 + t];
+    for (int t = NT + tid; t < nq; t += NT) spq[t] = hp.gpairs[q0 + t];
 #pragma unroll 1
-    for (int t = NT + tid; t < nc; t += NT) scn[t] = a.gcon[c0 + t];
+    for (int t = NT + tid; t < nc; t += NT) scn[t] = hp.gcon[c0 + t];
 #pragma unroll 1
-    for (int t = NT + tid; t < kGIntr * C; t += NT) ktab[t] = a.kintr[t];
+    for (int t = NT + tid; t < kGIntr * C; t += NT) ktab[t] = hp.kintr[t];
     __syncthreads();
     SSTAMP(stp, 1, 0);
+    // what the later phases read of the other arguments: from here on (no scalar wait inside the batch above)
+    const LinArgs& a = kernarg_at<LinArgs>(kGArgLin);
     if (pending) {
         for (int t = tid; t < 6 * gne; t += NT) {
             const int le = t / 6, k = t % 6;
@@ -989,7 +1042,7 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
                 for (int i = 0; i < 6; ++i) y[i] = y0[i];
             } else {
                 gbl = sgb[le];
-                const double* Ye = a.Y + 36 * (size_t)(ge0 + le);
+                const double* Ye = hp.Y + 36 * (size_t)(ge0 + le);
 #pragma unroll
                 for (int i = 0; i < 6; ++i) y[i] = Ye[6 * i + k];
             }
@@ -1031,7 +1084,7 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
             for (int le = sph0[pq]; le < sph0[pq + 1]; ++le) t -= spart[6 * le + pk];
             const float G = (float)(alpha_prev * t);   // G = alpha*delta -> CV_32F (:491-496)
             xn = xo + G;                                // x = x + G (:501)
-            a.x[m + 6 * (size_t)(p0 + pq) + pk] = xn;
+            hp.x[m + 6 * (size_t)(p0 + pq) + pk] = xn;
             Gk = (double)G;
         }
         sxn[16 * pq + pk] = (double)xn;
@@ -1047,11 +1100,11 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
                 g2 += xs[8 + q] * xs[8 + q];
                 x2 += xs[q] * xs[q];
             }
-            a.photo_norm[2 * (size_t)(p0 + pq)] = g2;
-            a.photo_norm[2 * (size_t)(p0 + pq) + 1] = x2;
+            hp.photo_norm[2 * (size_t)(p0 + pq)] = g2;
+            hp.photo_norm[2 * (size_t)(p0 + pq) + 1] = x2;
             pn0 = make_double2(g2, x2);
         }
-        if (a.fold) {   // (sxn's pad words) the folded norm chunk's input, written after the Cholesky
+        if (fold) {   // (sxn's pad words) the folded norm chunk's input, written after the Cholesky
             sxn[16 * pq + 6] = pn0.x;
             sxn[16 * pq + 7] = pn0.y;
         }
@@ -1126,10 +1179,10 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
                 else
                     pinhole_corner<RATIONAL, PRISM>(R, T, kd, fx, fy, cx, cy, X, Y, Z, Yr, u, v, D, Pq + 30);
                 const float euf = ou - u, evf = ov - v;   // fl32(imagePoints - imagePoints2)
-                if (a.resid) {
+                if (hp.resid) {
                     const size_t c = (size_t)info.z + cc0 + i;
-                    a.resid[2 * c] = euf;
-                    a.resid[2 * c + 1] = evf;
+                    hp.resid[2 * c] = euf;
+                    hp.resid[2 * c + 1] = evf;
                 }
                 const double eu = euf, ev2 = evf;
                 double ju[6], jv[6];   // J' rows: [Y x d, d]
@@ -1267,15 +1320,15 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
             double t = 0.0;
 #pragma unroll
             for (int i = j; i < 6; ++i) t += Li[i][j] * vv[i];
-            a.zp[6 * (size_t)photo + j] = t;
-            a.gp_tot[6 * (size_t)photo + j] = gs[j];
+            hp.zp[6 * (size_t)photo + j] = t;
+            hp.gp_tot[6 * (size_t)photo + j] = gs[j];
             sv[6 * q + j] = vv[j];
         }
         double2* L2 = reinterpret_cast<double2*>(sLi + 36 * q);
 #pragma unroll
         for (int k = 0; k < 18; ++k) L2[k] = make_double2(Li[(2 * k) / 6][(2 * k) % 6], Li[(2 * k + 1) / 6][(2 * k + 1) % 6]);
         if (bad || photo == a.fault_photo) atomicOr(&st->error, kErrPhotoNotPD);
-        if (a.fold) {   // the norm chunk's input: ||G||^2, ||x||^2 and the not-PD flag (sc1, each word its flag)
+        if (fold) {   // the norm chunk's input: ||G||^2, ||x||^2 and the not-PD flag (sc1, each word its flag)
             double* fw = a.fnorm + 4 * (size_t)photo;
             st_sc1_x2(fw, sxn[16 * q + 6], sxn[16 * q + 7]);
             st_sc1(fw + 2, bad || photo == a.fault_photo ? 1.0 : 0.0);
@@ -1307,7 +1360,7 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
             for (int k = j; k < 6; ++k) w += u[k] * li[6 * k + j];
             y[j] = w;
         }
-        double2* G2 = reinterpret_cast<double2*>(a.Y + 36 * (size_t)(ge0 + le) + 6 * i);
+        double2* G2 = reinterpret_cast<double2*>(hp.Y + 36 * (size_t)(ge0 + le) + 6 * i);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             H2[q] = make_double2(u[2 * q], u[2 * q + 1]);
@@ -1399,19 +1452,28 @@ __device__ __forceinline__ bool group_body(const LinArgs& a, const int grp) {
 // instantiation: remapping the index in the product kernel cost its register allocation ~230 more
 // SGPR-spill reloads and config4 ~0.2-0.4 us per step.
 template <int MODEL, bool RATIONAL, int PRISM, bool BACK, int L, bool FIRST = false>
-__global__ __launch_bounds__(kGroupRound * L, MCC_GROUP_OCC * 16 / L) void k_group(LinArgs a) {
+__global__ __launch_bounds__(kGroupRound * L, MCC_GROUP_OCC * 16 / L) void k_group(
+    State* st, const int* ghdr, const int n_pgroups, const unsigned flags, const int n_items, const int fold_parts,
+    long long, long long, long long, long long, LinArgs, GroupHot) {
+    // (the parameters ahead of LinArgs: GroupLead, mcc_internal.h -- preloaded into SGPRs, so the role
+    // dispatch below waits for nothing but a trailing workgroup's state->done; each role reads the two
+    // structs through kernarg_at, behind its own branch)
     constexpr int NT = kGroupRound * L;
     static_assert(L == 16 || L == 32, "k_group: 16 or 32 lanes per edge");
-    State* st = a.state;
+    static_assert(GSame<decltype(&k_group<MODEL, RATIONAL, PRISM, BACK, L, FIRST>), GroupKernelFn>::v,
+                  "k_group's parameters are GroupKernelFn's: kernarg_at's offsets are computed from that list");
+    long long t_entry = 0;   // MCC_DIAG: this wave's clock at the kernel's first instruction
+    WSTAMP(t_entry);
     const int tid = threadIdx.x;
+    const bool spare = (flags & kGLeadSsinv) != 0, fold = (flags & kGLeadFold) != 0;
     int grp = blockIdx.x;
     if (FIRST) {   // (test layout: the trailing workgroups first, then the groups)
-        const int nlead = (int)gridDim.x - a.n_pgroups;
-        grp = grp < nlead ? a.n_pgroups + grp : grp - nlead;
+        const int nlead = (int)gridDim.x - n_pgroups;
+        grp = grp < nlead ? n_pgroups + grp : grp - nlead;
     }
-    if (a.ssinv && grp == a.n_pgroups) {   // the spare workgroup: the previous system's inverse (m <= 30 warm solve)
+    if (spare && grp == n_pgroups) {   // the spare workgroup: the previous system's inverse (m <= 30 warm solve)
         extern __shared__ __attribute__((aligned(16))) double smem_spare[];
-        small_inverse(a, smem_spare, false);
+        small_inverse(kernarg_at<LinArgs>(kGArgLin), smem_spare, false);
         return;
     }
     // the folded reduction's task (item, norm chunk, the final): a trailing workgroup's by its index, or
@@ -1420,25 +1482,29 @@ __global__ __launch_bounds__(kGroupRound * L, MCC_GROUP_OCC * 16 / L) void k_gro
     // tilted sensor's variants: at 256 VGPRs the ticket tail tipped their sweep into a spill; the host
     // keeps the trailing task workgroups there.)
     int task;
-    if (a.fold && grp > a.n_pgroups - (a.ssinv ? 0 : 1)) {
+    if (fold && grp > n_pgroups - (spare ? 0 : 1)) {
         if (st->done) return;
-        task = grp - a.n_pgroups - (a.ssinv ? 1 : 0);
+        task = grp - n_pgroups - (spare ? 1 : 0);
     } else {
-        if (!group_body<MODEL, RATIONAL, PRISM, BACK, L>(a, grp) || PRISM == 2 || !a.fold_dyn) return;
+        if (!group_body<MODEL, RATIONAL, PRISM, BACK, L>(st, ghdr, fold, grp, t_entry) || PRISM == 2 ||
+            !(flags & kGLeadFoldDyn))
+            return;
         __shared__ int s_task;
         __syncthreads();   // the group's LDS is free
         if (tid == 0) {
-            const int t = __hip_atomic_fetch_add(a.fold_ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            int* ticket = kernarg_at<LinArgs>(kGArgLin).fold_ticket;
+            const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // the last taker resets the ticket for the next launch (every other taker has drawn)
-            if (t == a.n_pgroups - 1) __hip_atomic_store(a.fold_ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t == n_pgroups - 1) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             s_task = t;
         }
         __syncthreads();
         task = s_task;
     }
-    if (task < a.fsa.n_items) fold_item(a, task);
-    else if (task < a.fold_parts) fold_chunk(a, task - a.fsa.n_items);
-    else if (task == a.fold_parts) fold_final<NT>(a);
+    const LinArgs& a = kernarg_at<LinArgs>(kGArgLin);
+    if (task < n_items) fold_item(a, task);
+    else if (task < fold_parts) fold_chunk(a, task - n_items);
+    else if (task == fold_parts) fold_final<NT>(a);
 }
 
 // ---------------------------------------------------------------- k_prep4

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "../../include/mcc.h"
 #include "mcc_layout.hpp"
 
@@ -183,6 +185,101 @@ struct LinArgs {
     const int* ghdr;          // [n_pgroups][kGHdrInts] per-group header (kGHdr*, mcc_layout.hpp)
     const double* kintr;      // [C][kGIntr] the cameras' intrinsics rows, the kernel's LDS layout in FP64
 };
+
+// k_group's kernel parameters are (the members of GroupLead, one parameter each; LinArgs; GroupHot).
+// The leading ones are what the role dispatch (spare / group / item / chunk / final) tests: as
+// separate pointer and int parameters at the front of the argument segment they can be preloaded into
+// SGPRs at wave start (a struct passed by value is not), so the dispatch waits for no load.  The block
+// is padded to 64 bytes: LinArgs, which the other kernels share, keeps its layout and its alignment
+// modulo 64 within the segment.
+constexpr unsigned kGLeadSsinv = 1u, kGLeadFold = 2u, kGLeadFoldDyn = 4u, kGLeadFoldDirect = 8u;
+constexpr int kGLeadPreload = 6;   // the parameters ahead of the padding (8 SGPRs)
+struct GroupLead {
+    State* state;
+    const int* ghdr;
+    int n_pgroups;
+    unsigned flags;       // kGLead*: ssinv != null, fold, fold_dyn, fold_direct (the last is carried
+                          // for the dispatch word's completeness only: no role tests it, the final
+                          // workgroup reads LinArgs::fold_direct with the rest of its arguments)
+    int n_items;          // fsa.n_items
+    int fold_parts;
+    long long pad[4];
+};
+static_assert(sizeof(GroupLead) == 64 && sizeof(GroupLead) % alignof(LinArgs) == 0,
+              "k_group: LinArgs follows the leading block at byte 64 of the argument segment");
+inline GroupLead group_lead(const LinArgs& a) {
+    return {a.state, a.ghdr, a.n_pgroups,
+            (a.ssinv ? kGLeadSsinv : 0u) | (a.fold ? kGLeadFold : 0u) | (a.fold_dyn ? kGLeadFoldDyn : 0u) |
+                (a.fold_direct ? kGLeadFoldDirect : 0u),
+            a.fsa.n_items, a.fold_parts, {0, 0, 0, 0}};
+}
+// What a group's phase 0 dereferences, contiguous behind LinArgs: the group path reads the block with
+// the state words and the header's ranges in ONE scalar round trip at its entry (mcc_group.hpp).
+// Every member is the LinArgs field of the same name (group_hot).
+struct GroupHot {
+    const int4* gpairs;
+    const unsigned* gcon;
+    const double* dg;
+    const double* kintr;
+    float* x;
+    const float* cam_rt;
+    const double* ds_rt;
+    double* zp;
+    double* photo_norm;
+    const int* gblock;
+    double* Y;
+    const float* obj_x; const float* obj_y; const float* obj_z;
+    const float* img_u; const float* img_v;
+    long long* stamps;
+    // (the later phases' and the cold loops': read here too, or the compiler hoists their loads, and
+    // a wait for them, into phase 0's vector batch)
+    const int4* edge_info;
+    const unsigned char* edge_lphoto;
+    double* gp_tot;
+    float* resid;
+    int global_dim, n_cams;
+};
+inline GroupHot group_hot(const LinArgs& a) {
+    return {a.gpairs, a.gcon, a.dg, a.kintr, a.x, a.cam_rt, a.ds_rt, a.zp, a.photo_norm, a.gblock, a.Y,
+            a.obj_x, a.obj_y, a.obj_z, a.img_u, a.img_v, a.stamps, a.edge_info, a.edge_lphoto, a.gp_tot, a.resid,
+            a.global_dim, a.n_cams};
+}
+// k_group's parameter list, ONE definition: the kernel is declared with it (mcc_group.hpp asserts its
+// type against GroupKernelFn), and the byte offsets at which the kernel reads LinArgs and GroupHot
+// from its argument segment (kernarg_at) are computed from this very list, each parameter at its
+// natural alignment as the code object lays them out.  A parameter added, dropped or reordered moves
+// the offsets with it, or fails one of the assertions below.
+using GroupKernelFn = void (*)(State*, const int*, int, unsigned, int, int, long long, long long, long long, long long,
+                               LinArgs, GroupHot);
+template <class T, class U> struct GSame { static constexpr bool v = false; };
+template <class T> struct GSame<T, T> { static constexpr bool v = true; };
+template <class T, class... P>
+constexpr int kernarg_offset_of(void (*)(P...)) {   // of the first parameter of type T; -1: none
+    const size_t sz[] = {sizeof(P)...}, al[] = {alignof(P)...};
+    const bool is[] = {GSame<T, P>::v...};
+    size_t off = 0;
+    for (size_t i = 0; i < sizeof...(P); ++i) {
+        off = (off + al[i] - 1) / al[i] * al[i];
+        if (is[i]) return (int)off;
+        off += sz[i];
+    }
+    return -1;
+}
+constexpr int kGArgLin = kernarg_offset_of<LinArgs>(GroupKernelFn(nullptr));
+constexpr int kGArgHot = kernarg_offset_of<GroupHot>(GroupKernelFn(nullptr));
+// the same list as a struct (what the host test and the launch function's helpers describe)
+struct GroupKernarg {
+    GroupLead lead;
+    LinArgs a;
+    GroupHot hot;
+};
+static_assert(kGArgLin == (int)offsetof(GroupKernarg, a) && kGArgLin == (int)sizeof(GroupLead) && kGArgLin % 64 == 0,
+              "k_group: LinArgs follows the 64-byte leading block");
+static_assert(kGArgHot == (int)offsetof(GroupKernarg, hot) && kGArgHot == kGArgLin + (int)sizeof(LinArgs),
+              "k_group: GroupHot follows LinArgs without padding");
+static_assert(kernarg_offset_of<unsigned>(GroupKernelFn(nullptr)) == (int)offsetof(GroupLead, flags) &&
+                  kernarg_offset_of<long long>(GroupKernelFn(nullptr)) == (int)offsetof(GroupLead, pad),
+              "k_group: the leading parameters lie as GroupLead's members do");
 
 // The m > 30 solve with the previous step's inverse (the "warm" solve, solve_large in
 // mcc_kernels.hip): a resident helper kernel on a side stream (k_sinv_helper) inverts each update

@@ -4731,12 +4731,18 @@ static hipError_t launch_group_t(const LinArgs& a, size_t shmem, hipStream_t s) 
     // + the spare workgroup of the m <= 30 warm solve (small_inverse)
     // (+ the folded reduction's item, norm-chunk and final workgroups)
     const dim3 grid(a.n_pgroups + (a.ssinv ? 1 : 0) + (a.fold && !a.fold_dyn ? a.fold_parts + 1 : 0));
+    // the leading (preloaded) parameters, LinArgs, the hot pointers of phase 0 (mcc_internal.h)
+    const GroupLead gl = group_lead(a);
+    const GroupHot gh = group_hot(a);
+#define MCC_GROUP_ARGS gl.state, gl.ghdr, gl.n_pgroups, gl.flags, gl.n_items, gl.fold_parts, 0LL, 0LL, 0LL, 0LL, a, gh
     if (a.fold_first) {   // (test layout, omnidir only: mcc_create)
         if (MODEL != MCC_MODEL_OMNI) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_group<MCC_MODEL_OMNI, false, false, false, L, true>), grid, dim3(kGroupRound * L), shmem, s, a);
+        hipLaunchKernelGGL((k_group<MCC_MODEL_OMNI, false, false, false, L, true>), grid, dim3(kGroupRound * L), shmem, s,
+                           MCC_GROUP_ARGS);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((k_group<MODEL, RATIONAL, PRISM, BACK, L>), grid, dim3(kGroupRound * L), shmem, s, a);
+    hipLaunchKernelGGL((k_group<MODEL, RATIONAL, PRISM, BACK, L>), grid, dim3(kGroupRound * L), shmem, s, MCC_GROUP_ARGS);
+#undef MCC_GROUP_ARGS
     return hipGetLastError();
 }
 template <int L>

@@ -6,7 +6,9 @@ diagnostic build (libmcc_diag.so).  Never quote this build's run time: read its 
 
 k_group (the split step's group kernel) group g -> row g slots 0..10 (start, loads, photo update and
 Rodrigues, round 0's prologue, sweep, chain, the later rounds, Hpp sums, Cholesky, U / Y', pairs), all
-stamped by wave 0; slots 16 + w wave w's last round's end and 24 + w its round-0 prologue, sweep and chain
+stamped by wave 0; slots 12 and 13 the clock at the kernel's first instruction as wave 0 and the last wave
+read it (printed as "entry -> stamp 0": the role dispatch, the stop test and the scalar loads, which the
+phase rows do not cover); slots 16 + w wave w's last round's end and 24 + w its round-0 prologue, sweep and chain
 ends, printed per wave half (wave_halves).
 Otherwise rows of the stamp buffer (32 slots each): k_photo photo p -> row p slots 0..5 (start, staged,
 Cholesky, U / Y', pairs stored; slot 2 unused); k_prep workgroup w -> row w slots 8..11 (start, update,
@@ -86,6 +88,16 @@ def main():
 
     if ba.step_kernels() == "k_group":
         ng = int(np.count_nonzero(s[:, 0]))
+        # the kernel's entry (slots 12, 13: wave 0's and the last wave's clock at k_group's first
+        # instruction): the role dispatch, the stop test and the scalar loads ahead of stamp 0
+        ok = (s[:, 0] > 0) & (s[:, 12] > 0) & (s[:, 13] > 0)
+        if ok.any():
+            print(f"k_group entry: {ok.sum()} groups")
+            print(f"  {'entry -> stamp 0':22s} {med(s[ok, 0] - s[ok, 12])}")
+            print(f"  {'entry -> stamp 1':22s} {med(s[ok, 1] - s[ok, 12])}")
+            lw = s[ok, 13] - s[ok, 12]
+            print(f"  last wave's entry minus wave 0's: median {np.median(lw):.0f}  p10 {np.percentile(lw, 10):.0f}  "
+                  f"p90 {np.percentile(lw, 90):.0f}")
         phases(list(range(11)), ["loads (round trip 1)", "photo update+Rodrigues", "edge prologue (r0)", "sweep (r0)",
                                  "butterfly+chain (r0)", "later rounds", "photo Hpp sums", "Cholesky", "U, Y'",
                                  "pairs+store"], f"k_group ({ng} groups)")

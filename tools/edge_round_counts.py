@@ -12,7 +12,11 @@ listing's own order (blocks the compiler moved behind the kernel's end, the cold
   chain      from the sweep loop's end to the next s_barrier (butterfly, record scatter, chain)
 Per region: VALU instructions, the FP64 ones among them, moves, selects and the remaining (integer,
 address, lane-crossing) VALU; --hist adds the FP64 opcode histogram, which a bit-neutral change must
-leave equal.  The kernel's VGPR count and SGPR spill count come from the listing's metadata."""
+leave equal.  The kernel's VGPR count and SGPR spill count come from the listing's metadata.
+
+    python3 tools/edge_round_counts.py part3.s [mangled-name substring] --entry [listing.txt]
+
+counts the scalar loads and waits of the kernel's entry and of phase 0's vector batch instead (entry())."""
 import collections
 import re
 import sys
@@ -52,10 +56,53 @@ def classify(ops):
     return c
 
 
+def entry(k, lines, pat, out):
+    """--entry [listing.txt]: the scalar side of the kernel's entry and of phase 0's vector batch.  Regions,
+    in the listing's order: 'entry' from the kernel's first line to its first global_load, 'batch' from
+    there to the end of the first round's corner loads (the second sched_barrier after it).  Counts
+    s_load and s_waitcnt lines only (every path the compiler laid out in the region, the other roles'
+    dispatch included); listing.txt gets the region's loads, waits, branches, labels and LDS stores up to
+    the first s_barrier with their line numbers (profiles/group_phase0's format)."""
+    ops = [op_of(l) for l in k]
+    first = next(i for i, o in enumerate(ops) if o and o.startswith("global_load"))
+    sb = [i for i in range(first, len(k)) if "sched_barrier" in k[i]]
+    bar = next(i for i, o in enumerate(ops) if o == "s_barrier")
+    end = sb[1] if len(sb) > 1 and sb[1] < bar else bar
+    print(f"kernel {pat}: first global_load at line {first + 1}, the batch ends at line {end + 1}, first s_barrier at {bar + 1}")
+    print(f"{'region':8s} {'s_load':>7s} {'s_waitcnt lgkmcnt':>18s} {'global_load':>12s} {'s_waitcnt vmcnt':>16s} {'branches':>9s}")
+    for name, a, b in (("entry", 0, first), ("batch", first, end)):
+        r = [(o, k[i]) for i, o in enumerate(ops[a:b], a) if o]
+        print(f"{name:8s} {sum(o.startswith('s_load') for o, _ in r):7d} "
+              f"{sum(o == 's_waitcnt' and 'lgkmcnt' in l for o, l in r):18d} "
+              f"{sum(o.startswith('global_load') for o, _ in r):12d} "
+              f"{sum(o == 's_waitcnt' and 'vmcnt' in l for o, l in r):16d} "
+              f"{sum(o.startswith(('s_cbranch', 's_branch')) for o, _ in r):9d}")
+    meta = "\n".join(lines)
+    for key in ("num_vgpr", "private_seg_size"):
+        m = re.search(re.escape(pat) + r"\S*\." + key + r", (\d+)", meta)
+        if m:
+            print(key, m.group(1))
+    for key in ("amdhsa_user_sgpr_kernarg_preload_length", "sgpr_spill_count"):
+        m = re.search(re.escape(pat) + r".*?" + key + r":?\s+(\d+)", meta, re.S)
+        if m:
+            print(key, m.group(1))
+    if out:
+        keep = re.compile(r"^\s+(s_load|s_waitcnt|s_cbranch|s_branch|global_load|ds_write|s_barrier|s_endpgm|; sched_barrier)|^\.LBB")
+        with open(out, "w") as f:
+            for i, l in enumerate(k[:bar + 1]):
+                if keep.match(l):
+                    f.write(f"{i + 1}:{l.split(';')[0].rstrip() if not l.strip().startswith(';') else l}\n")
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     hist = "--hist" in sys.argv
     lines = open(args[0]).read().splitlines()
+    if "--entry" in sys.argv:
+        pat = args[1] if len(args) > 1 and not args[1].endswith(".txt") else DEFAULT
+        out = next((a for a in args[1:] if a.endswith(".txt")), None)
+        entry(kernel_text(lines, pat), lines, pat, out)
+        return
     pat = args[1] if len(args) > 1 else DEFAULT
     k = kernel_text(lines, pat)
     ops = [op_of(l) for l in k]

@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / occupancy table of mcc_kernels.hip (hipcc -Rpass-analysis=
-kernel-resource-usage, device-only compile).  Usage: python tools/kres.py [filter]"""
+kernel-resource-usage, device-only compile, per part with the Makefile's flags).  Usage: python tools/kres.py [filter]"""
 import re
 import subprocess
 import sys
 
 ROOT = __file__.rsplit("/tools/", 1)[0]
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function",
-       "--cuda-device-only", "-c", f"{ROOT}/multi_camera_calibration_amd/csrc/mcc_kernels.hip", "-o", "/tmp/kres.o",
-       "-Rpass-analysis=kernel-resource-usage"]
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+# compiled as the Makefile compiles the library: once per part, the k_group parts (2, 3) with their
+# kernel-argument preload
+PRELOAD = {2: ["-mllvm", "-amdgpu-kernarg-preload-count=6"], 3: ["-mllvm", "-amdgpu-kernarg-preload-count=6"]}
+out = ""
+for part in range(6):
+    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function",
+           f"-DMCC_PART={part}"] + PRELOAD.get(part, []) + [
+           "--cuda-device-only", "-c", f"{ROOT}/multi_camera_calibration_amd/csrc/mcc_kernels.hip", "-o", "/tmp/kres.o",
+           "-Rpass-analysis=kernel-resource-usage"]
+    out += subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
