@@ -343,15 +343,16 @@ def init_camera_matrix(off, obj, img, image_size, aspect_ratio=0.0):
 
 
 def calibrate_camera(off, obj, img, image_size, K=None, D=None, flags=0, nd=5, max_count=30, eps=2.2e-16, device=0,
-                     return_ms=False):
+                     return_ms=False, crit_type=MCC_CRIT_COUNT_EPS):
     """cv::calibrateCamera for one pinhole camera on the GPU (mcc_calibrate_camera): view v owns corners
     off[v]:off[v + 1] of obj [corners, 3] and img [corners, 2] (pixels); image_size = (width, height); flags are
     cv::CALIB_*'s (CV_CALIB_* above; the omnidir CALIB_* below are another set); nd in {4, 5, 8}.  K and D are the guess with CV_CALIB_USE_INTRINSIC_GUESS (K also
     gives the ratio under CV_CALIB_FIX_ASPECT_RATIO).  Returns (rms, K [3, 3], D [nd], rvec [V, 3], tvec [V, 3],
     view_rms [V], iterations, status): the least-squares minimum of the reprojection error by Levenberg-Marquardt,
-    stopped after max_count accepted steps or a relative step below eps; status CALIB_CONVERGED, CALIB_COUNT or
-    CALIB_STALLED.  With return_ms the loop's device milliseconds and its number of trials are appended."""
-    d, keep = _calib_desc(off, obj, img, image_size, flags, nd, MCC_CRIT_COUNT_EPS, max_count, eps, device)
+    stopped after max_count accepted steps or a relative step below eps (crit_type: MCC_CRIT_COUNT, MCC_CRIT_EPS or
+    both; with MCC_CRIT_EPS alone max_count is not read); status CALIB_CONVERGED, CALIB_COUNT or CALIB_STALLED.
+    With return_ms the loop's device milliseconds and its number of trials are appended."""
+    d, keep = _calib_desc(off, obj, img, image_size, flags, nd, crit_type, max_count, eps, device)
     Kio = np.zeros((3, 3)) if K is None else np.array(K, np.float64).reshape(3, 3)
     Dio = np.zeros(max(int(nd), 1))
     if D is not None:

@@ -76,6 +76,7 @@ def make(corners, seed, noise=0.0, relief=0.0, g=G_TRUE):
 
 # cv::CALIB_* (include/mcc.h: MCC_CALIB_*)
 USE_GUESS, FIX_ASPECT, FIX_PP, ZERO_TANGENT, FIX_FOCAL, FIX_K1, FIX_K2, FIX_K3, RATIONAL = 1, 2, 4, 8, 16, 32, 64, 128, 16384
+FIX_K4, FIX_K5, FIX_K6 = 2048, 4096, 8192
 ALL_FIXED = USE_GUESS | FIX_PP | ZERO_TANGENT | FIX_FOCAL | FIX_K1 | FIX_K2 | FIX_K3
 
 
@@ -99,7 +100,73 @@ def noisy_cases():
             ("principal", c, FIX_PP | USE_GUESS, 5, pp),
             ("aspect", c, FIX_ASPECT, 5, None),
             ("focal", c, FIX_FOCAL | USE_GUESS, 5, fl),
-            ("relief", make([88] * 17, seed=189, noise=0.2, relief=30.0), USE_GUESS, 5, off1)]
+            ("relief", make([88] * 17, seed=189, noise=0.2, relief=30.0), USE_GUESS, 5, off1),
+            # unequal corner counts under noise: idle lanes (6, 20), 1024 corners, a view's sum in its own slot
+            ("ragged9", make(RAGGED, seed=177, noise=0.2), 0, 5, None),
+            ("nd4", c, 0, 4, None),
+            ("fix_k1_k2", c, USE_GUESS | FIX_K1 | FIX_K2, 5, off1)]
+    return out
+
+
+def step_cases():
+    """(name, case, flags, nd, guess) of tests/test_calibrate_camera_steps.py and tests/test_pincalib_step_cpu.py:
+    the smallest inputs whose Levenberg-Marquardt trajectory from the guess reaches each path of the trial
+    kernels.  Every one starts from a guess (USE_GUESS is in the flags), so that state 0 is known."""
+    far = make(RAGGED, seed=77, noise=0.2)
+    g_far = far.g.copy()
+    g_far[0:2] *= 1.5                 # far enough for a rejected trial: the stored sums are read again
+    asp = make([65] * 17, seed=165, noise=0.2)
+    nd4 = make([20] * 5, seed=129, noise=0.2)          # groups of 3 + 2 views
+    g_nd4 = nd4.g.copy()
+    g_nd4[0:2] *= 1.5                 # from 1 % off this case is at its minimum after five steps, and the sixth
+    #                                   decision is no longer clear (MARGIN); from here all six steps are far from it
+    rat = make([88] * 10, seed=310, g=G_RATIONAL)      # exact: k4 .. k6 are not determined under noise
+    four = make([4] * 65, seed=465, noise=0.2)         # groups of 9 views, the last of 2
+    return [("ragged9/far", far, USE_GUESS, 5, g_far),
+            ("17x65/aspect", asp, USE_GUESS | FIX_ASPECT, 5, asp.g * 1.05),
+            ("5x20/nd4_pp", nd4, USE_GUESS | FIX_PP, 4, g_nd4),
+            ("10x88/rational_k5", rat, USE_GUESS | RATIONAL | FIX_K5, 8, rat.g * 1.01),
+            ("65x4", four, USE_GUESS, 5, four.g * 1.01)]
+
+
+# What the step tests walk and where they compare a step with npcalib.lm_step (DESIGN.md 7g):
+K_STEPS = 6        # accepted steps from the start
+GAMMA_MIN = 1e-4   # below it J^T e is mostly cancellation; its rounding, about 1e-16 / gamma relative, would set rho
+RMS_MIN = 1e-4     # px.  A residual is a difference of pixels near 1.3e3, so an entry carries about 2^-53 * 1.3e3 =
+#                    1.4e-13 px of rounding, 1.4e-9 of an rms of 1e-4 px: under that (exact data only, close to the
+#                    minimum) the residual's own rounding would set rho, whatever the solver does
+MARGIN = 1e-9      # every accept / reject decision on these walks has |en / err - 1| >= MARGIN: the device and the
+#                    reference differ near 1e-14 there, so both take the same one
+
+
+def step_checked(gamma, rms):
+    return gamma >= GAMMA_MIN and rms >= RMS_MIN
+
+
+def state0(flags, nd, guess):
+    """The globals mcc_calibrate_camera starts from under USE_GUESS, and the aspect ratio it holds: the guess
+    with p1 = p2 = 0 under ZERO_TANGENT, k3 = 0 at nd = 4, the slots past nd at 0 and fx = a fy under FIX_ASPECT."""
+    g = np.zeros(12)
+    g[:4 + nd] = np.asarray(guess, np.float64)[:4 + nd]
+    aspect = float(g[0] / g[1]) if flags & FIX_ASPECT else 0.0
+    if flags & ZERO_TANGENT:
+        g[6:8] = 0.0
+    if nd == 4:
+        g[8] = 0.0
+    if aspect > 0:
+        g[0] = aspect * g[1]
+    return g, aspect
+
+
+def lm_lambdas(rejections):
+    """lambda at the start of every accepted step, given the rejections before each: the documented policy from
+    1e-3, x 10 on a rejection, x 0.1 floored at 1e-12 on an accepted step."""
+    lam, out = 1e-3, []
+    for r in rejections:
+        out.append(lam)
+        for _ in range(r):
+            lam = lam * 10.0
+        lam = max(lam * 0.1, 1e-12)
     return out
 
 

@@ -9,7 +9,8 @@
 //   the loop: k_pc_lin / k_pc_try's sequence on exact data (views x corners 3 x 20 and 5 x 88, nd 5 and 8), with
 //   the contributions summed in view order, started 2 % off the truth: Levenberg-Marquardt with the kernels'
 //   policy reaches rms < 1e-9 px and the true fx fy cx cy to 1e-6 relative.  The lanes' summation order and
-//   the tickets exist only on the GPU: tests/test_calibrate_camera.py covers those.
+//   the tickets exist only on the GPU: tests/test_calibrate_camera.py covers those, and
+//   tests/test_calibrate_camera_steps.py compares every step with an independently computed one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -12,7 +12,8 @@ solvers differ by their stopping points.  Against npcalib the recorded figure is
 reference's own resolution, whichever is larger: calib_cases.REF_RESOLUTION, constants measured once (the
 largest last Gauss-Newton step and the largest gamma at its own minimum over the noisy cases), which
 tests/test_calibrate_camera_cpu.py holds npcalib to; a difference below them says nothing about the device.
-Every test prints its figures before it asserts.
+Every test prints its figures before it asserts.  Whether each step on the way is the right one is
+tests/test_calibrate_camera_steps.py's question.
 """
 import json
 
@@ -39,6 +40,7 @@ MEASURED = {
     "exact/ragged9": dict(dK=6.05e-16, dD=3.51e-14, dr=2.55e-15, dt=4.55e-13),
     "exact/65x20": dict(dK=1.94e-15, dD=5.49e-14, dr=2.05e-15, dt=1.59e-12),
     "exact/10x20": dict(dK=1.18e-14, dD=9.30e-12, dr=9.38e-15, dt=8.60e-12),
+    "exact/24x4": dict(dK=2.43e-14, dD=1.11e-09, dr=4.15e-14, dt=2.66e-11),
     "noisy/17x64": dict(dK=4.10e-09, dD=2.60e-07, dr=2.10e-09, dt=2.56e-06, gamma=3.59e-08),
     "noisy/17x65": dict(dK=1.44e-09, dD=3.37e-08, dr=8.33e-10, dt=9.12e-07, gamma=2.61e-08),
     "noisy/17x88": dict(dK=1.28e-09, dD=2.64e-10, dr=6.62e-10, dt=6.91e-07, gamma=2.69e-08),
@@ -47,17 +49,21 @@ MEASURED = {
     "noisy/aspect": dict(dK=4.19e-10, dD=8.77e-10, dr=2.16e-10, dt=2.26e-07, gamma=2.34e-08),
     "noisy/focal": dict(dK=4.64e-10, dD=1.02e-10, dr=3.40e-10, dt=3.51e-07, gamma=2.18e-08),
     "noisy/relief": dict(dK=3.80e-10, dD=4.08e-10, dr=2.94e-10, dt=3.26e-07, gamma=1.56e-08),
+    "noisy/ragged9": dict(dK=6.06e-10, dD=4.54e-09, dr=3.42e-10, dt=3.19e-07, gamma=2.57e-08),
+    "noisy/nd4": dict(dK=8.31e-10, dD=3.09e-11, dr=4.18e-10, dt=4.48e-07, gamma=6.38e-09),
+    "noisy/fix_k1_k2": dict(dK=3.11e-10, dD=7.24e-11, dr=2.18e-10, dt=2.20e-07, gamma=1.20e-08),
     "all_fixed": dict(dr=0.00e+00, dt=0.00e+00),
     "rational": dict(proj_over_gate=1.37e-05),
     "permuted": dict(dr=1.02e-10, dt=1.14e-07),
 }
 
 
-def run(c, flags=0, nd=5, guess=None, K=None, max_count=MAXC, eps=EPS):
+def run(c, flags=0, nd=5, guess=None, K=None, max_count=MAXC, eps=EPS, crit_type=api.MCC_CRIT_COUNT_EPS):
     D = None
     if guess is not None:
         K, D = CC.guess_KD(guess, nd)
-    return api.calibrate_camera(c.off, c.obj, c.img, CC.SIZE, K=K, D=D, flags=flags, nd=nd, max_count=max_count, eps=eps)
+    return api.calibrate_camera(c.off, c.obj, c.img, CC.SIZE, K=K, D=D, flags=flags, nd=nd, max_count=max_count, eps=eps,
+                                crit_type=crit_type)
 
 
 def globals_of(K, D):
@@ -100,6 +106,18 @@ def test_exact_data_from_the_closed_form_start(name):
     check("exact/" + name, fig)
 
 
+def test_exact_four_corner_views_from_a_guess():
+    """The documented minimum of four corners per view: 24 views, a guess 1 % off."""
+    c = CC.make([4] * 24, seed=328)
+    res = run(c, CC.USE_GUESS, 5, c.g * 1.01)
+    fig = figures(res, c.g, c.poses)
+    fig.update(rms=res[0], iterations=res[6], status=res[7])
+    check("exact/24x4", fig, keys=())
+    assert res[0] <= 1e-8
+    assert np.all(np.isfinite(res[5])) and np.all(res[5] <= 1e-8 * np.sqrt(len(c.obj)))
+    check("exact/24x4", fig)
+
+
 NOISY = {x[0]: x for x in CC.noisy_cases()}
 _REF = {}
 
@@ -135,6 +153,15 @@ def test_noisy_data_reaches_the_reference_minimum(name):
     assert fig["gamma"] <= 1e-4
     check("noisy/" + name, fig, keys=("gamma", "dK", "dD", "dr", "dt"), against_reference=True)
     assert abs(np.sqrt((res[5] ** 2 * np.diff(c.off)).sum() / len(c.obj)) - rms) <= 1e-12 * rms
+    # every view's rms against the reference's projection at the returned parameters: a view's error in its own slot
+    e = npcalib.residuals(c, globals_of(K, D), np.hstack([rvec, tvec])).reshape(-1, 2)
+    vr = np.array([np.sqrt((e[c.view(v)] ** 2).sum() / (c.off[v + 1] - c.off[v])) for v in range(c.n_views)])
+    print("FIG", json.dumps({"case": name, "dview": float(np.max(np.abs(res[5] - vr) / vr))}))
+    assert np.all(np.abs(res[5] - vr) <= 1e-9 * vr)
+    if name == "nd4":
+        assert len(D) == 4
+    if name == "fix_k1_k2":
+        assert D[0] == guess[4] and D[1] == guess[5]                # bit-equal to the input
     if name == "principal":
         assert K[0, 2] == guess[2] and K[1, 2] == guess[3]          # bit-equal to the input
     if name == "focal":
@@ -211,6 +238,19 @@ def test_one_accepted_step():
     res = run(c, max_count=1)
     assert res[6] == 1 and res[7] == api.CALIB_COUNT
     assert np.isfinite(res[0]) and res[0] < 10.0   # one step from the closed-form start
+
+
+def test_the_stop_criteria_one_at_a_time():
+    # exact data: a noisy case such as 17x88 ends "stalled" at its minimum when eps is 1e-13 (ten trials in a row
+    # that rounding rejects), whichever criteria are set; exact/3x88 converges in 9 steps under both
+    c = CC.make(EXACT["3x88"], seed=300 + 3 + 88)
+    count = run(c, max_count=3, eps=1.0, crit_type=api.MCC_CRIT_COUNT)      # eps is not read
+    both = run(c, max_count=3, eps=1.0, crit_type=api.MCC_CRIT_COUNT_EPS)
+    eps = run(c, max_count=1, eps=1e-13, crit_type=api.MCC_CRIT_EPS)        # max_count is not read
+    print("FIG", json.dumps({"case": "criteria", "count": count[6:8], "both": both[6:8], "eps": eps[6:8]}))
+    assert count[6] == 3 and count[7] == api.CALIB_COUNT
+    assert both[6] == 1 and both[7] == api.CALIB_CONVERGED
+    assert eps[6] > 1 and eps[7] == api.CALIB_CONVERGED
 
 
 def test_a_single_fronto_parallel_view_ends():

@@ -133,6 +133,18 @@ def test_reference_recovers_the_truth_on_exact_data():
     assert np.abs(poses - c.poses)[:, :3].max() <= 1e-9 and np.abs(poses - c.poses)[:, 3:].max() <= 1e-9 * 1200
 
 
+def test_reference_recovers_four_corner_views():
+    """exact/24x4 of tests/test_calibrate_camera.py: four corners per view still determine the problem."""
+    c = CC.make([4] * 24, seed=328)
+    mask = api.calib_mask(CC.USE_GUESS, 5)
+    g, poses, r, steps = npcalib.gauss_newton(c, c.g * np.where(mask, 1.0 + 1e-3, 1.0), c.poses * (1 + 1e-4), mask)
+    rel = np.abs(g - c.g)[:4] / c.g[:4]
+    print("steps", steps, "rms", r, "K rel", rel.max(), "D abs", np.abs(g - c.g)[4:].max(), "pose", np.abs(poses - c.poses).max())
+    assert steps <= 20 and r <= 1e-9
+    assert rel.max() <= 1e-9 and np.abs(g - c.g)[4:].max() <= 1e-7   # (k3 rests on r^6 of a 40 mm square)
+    assert np.abs(poses - c.poses)[:, :3].max() <= 1e-9 and np.abs(poses - c.poses)[:, 3:].max() <= 1e-9 * 1200
+
+
 @pytest.mark.parametrize("case", CC.noisy_cases(), ids=lambda x: x[0])
 def test_reference_converges_on_the_noisy_cases(case):
     name, c, flags, nd, guess = case

@@ -5,7 +5,8 @@ and k_pc_try runs for a view -- for the host with one lane and checks the analyt
 against central differences of pnp_residual, the masked and aspect-coupled global rows, and the whole
 Levenberg-Marquardt trial sequence (three-pass linearisation, damped elimination, reduced 12 x 12 solve,
 back-substitution, accept / reject) on exact data.  The lanes' summation order and the tickets exist only on
-the GPU: tests/test_calibrate_camera.py covers those."""
+the GPU: tests/test_calibrate_camera.py covers those, and tests/test_calibrate_camera_steps.py compares every
+step with an independent one (tests/test_pincalib_step_cpu.py does that for one lane)."""
 import os
 import subprocess
 
