@@ -341,6 +341,68 @@ int mcc_init_camera_matrix(const mcc_calib_desc *d, double aspect_ratio, double 
 int mcc_calibrate_camera(const mcc_calib_desc *d, double *K, double *D, double *rvec, double *tvec,
                          double *view_rms, double *rms, int *iterations, int *status, double *device_ms);
 
+/* ---- pinhole stereo pair: cv::stereoCalibrate.  View v is seen by both cameras (img1, img2: the same
+ * corners in the same order); camera 2 sees it at R2 = R R_v, t2 = R t_v + T, where (R_v, t_v) is its pose in
+ * camera 1 and R = exp(om).  The unknowns are the poses, the rig (om, T) and 12 intrinsic slots per camera:
+ * 30 global slots om T | fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 of camera 1 | the same of camera 2.  The
+ * result is the least-squares minimum of both cameras' reprojection error through cv::projectPoints' model
+ * under the flags, by mcc_calibrate_camera's Levenberg-Marquardt policy on the device (sums in view order:
+ * two calls give the same bits).  Bit parity with OpenCV is not claimed.
+ * Flags: the MCC_CALIB_* above, applied to both cameras (under FIX_ASPECT_RATIO each camera's fx follows its
+ * own fy by its own input ratio), and the three below; any other bit is MCC_EINVAL. */
+#define MCC_CALIB_FIX_INTRINSIC 256              /* all 24 intrinsic slots stay at their input values */
+#define MCC_CALIB_SAME_FOCAL_LENGTH 512          /* camera 2's fx, fy follow camera 1's; the start is the inputs' mean */
+#define MCC_CALIB_USE_EXTRINSIC_GUESS (1 << 22)  /* R, T on input are the rig's start */
+
+typedef struct mcc_stereo_calib_desc {
+    int n_views;
+    const int *view_off;     /* [n_views+1] corner offsets; 4 to 1024 corners per view */
+    const double *obj;       /* [3*corners] object points                              */
+    const double *img1;      /* [2*corners] camera 1's corners (pixels)                */
+    const double *img2;      /* [2*corners] camera 2's                                 */
+    int image_width, image_height;
+    int flags;               /* MCC_CALIB_*                                            */
+    int nd;                  /* 4, 5 or 8 distortion coefficients, both cameras        */
+    int crit_type;           /* MCC_CRIT_*; cv::stereoCalibrate's default is COUNT_EPS, 30, 1e-6 */
+    int max_count;           /* accepted steps at most (MCC_CRIT_EPS alone: 1000)      */
+    double eps;
+    int device;
+    int *trials;             /* out, may be NULL: trials run (one k_ps_lin + k_ps_try pair each, accepted or not) */
+} mcc_stereo_calib_desc;
+
+/* The 0/1 mask of free slots over the 30 global slots, and for every slot the slot it follows (-1: none):
+ * fx follows its camera's fy under FIX_ASPECT_RATIO; under SAME_FOCAL_LENGTH camera 2's fy follows camera
+ * 1's fy and its fx camera 1's fx (or its own fy by its own ratio with FIX_ASPECT_RATIO).  A slot that
+ * follows another is not free.  Host only.  MCC_EINVAL for an unknown flag bit or a bad nd. */
+int mcc_stereo_calib_mask(int flags, int nd, int *mask /* [30] */, int *tie /* [30] */);
+
+/* The rig's start from both cameras' poses of every view (rvec, tvec [3*n_views] each), cv::stereoCalibrate's
+ * rule: the component-wise median over the views of the rotation vector of R_2v R_1v^T and of
+ * t_2v - R_2v R_1v^T t_1v (the middle value, or the mean of the middle two).  Host only. */
+int mcc_stereo_init_extrinsics(int n_views, const double *rvec1, const double *tvec1, const double *rvec2,
+                               const double *tvec2, double *om /* [3] */, double *T /* [3] */);
+
+/* E[9] = [T]x R and F[9] = K2^-T E K1^-1, scaled so that F[8] = 1 when it is not 0, as mcc_stereo_calibrate
+ * returns them (each may be NULL).  Host only. */
+int mcc_stereo_epipolar(const double *R /* [9] */, const double *T /* [3] */, const double *K1 /* [9] */,
+                        const double *K2 /* [9] */, double *E, double *F);
+
+/* K1[9], D1[nd], K2[9], D2[nd] are in/out.  With FIX_INTRINSIC or USE_INTRINSIC_GUESS they are the start
+ * and both cameras' pose seeds come from one internal mcc_solve_pnp_batch; otherwise two internal
+ * mcc_calibrate_camera calls (the per-camera flags, the caller's criteria) give the intrinsics and the seeds,
+ * and only the aspect ratio under FIX_ASPECT_RATIO is read from K1, K2.  The rig starts at R[9], T[3] with
+ * USE_EXTRINSIC_GUESS, else at mcc_stereo_init_extrinsics'; the view poses start at camera 1's.
+ * Out, each may be NULL: R[9], T[3], E[9] = [T]x R, F[9] = K2^-T E K1^-1 scaled to F[8] = 1 when that is
+ * not 0 (E and F on the host), rvec / tvec [3*n_views] (camera 1's), view_rms[2*n_views] (view v's RMS in
+ * camera 1, then in camera 2), rms = sqrt(sum |e|^2 / (2 corners)), iterations, status (MCC_CALIB_*),
+ * device_ms.  MCC_EINVAL, before any device work, for a null pointer, n_views < 1, a view of fewer than 4
+ * or more than 1024 corners, a bad nd, an unknown flag bit, a zero focal length in K1 or K2 under
+ * FIX_INTRINSIC or FIX_ASPECT_RATIO, or USE_EXTRINSIC_GUESS without R and T; a view without a pose seed
+ * fails the call with its index and camera. */
+int mcc_stereo_calibrate(const mcc_stereo_calib_desc *d, double *K1, double *D1, double *K2, double *D2,
+                         double *R, double *T, double *E, double *F, double *rvec, double *tvec,
+                         double *view_rms, double *rms, int *iterations, int *status, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif

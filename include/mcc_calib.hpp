@@ -14,6 +14,8 @@
  * Levenberg-Marquardt on the GPU; bit parity with OpenCV is not claimed.  distCoeffs has 8 entries
  * with CALIB_RATIONAL_MODEL and 5 otherwise (a vector handed in with another size is resized; its leading entries
  * are the guess under CALIB_USE_INTRINSIC_GUESS).  Thin-prism and tilted-sensor flags throw.
+ *
+ * cv::stereoCalibrate for a pinhole pair is further down, over mcc_stereo_calibrate.
  */
 #ifndef MCC_CALIB_HPP
 #define MCC_CALIB_HPP
@@ -68,6 +70,42 @@ double calibrateCamera(const std::vector<std::vector<Vec3d>>& objectPoints,
 std::array<double, 9> initCameraMatrix2D(const std::vector<std::vector<Vec3d>>& objectPoints,
                                          const std::vector<std::vector<Vec2d>>& imagePoints, Size imageSize,
                                          double aspectRatio = 1.0);
+
+// cv::stereoCalibrate's own flags
+enum {
+    CALIB_FIX_INTRINSIC = MCC_CALIB_FIX_INTRINSIC,
+    CALIB_SAME_FOCAL_LENGTH = MCC_CALIB_SAME_FOCAL_LENGTH,
+    CALIB_USE_EXTRINSIC_GUESS = MCC_CALIB_USE_EXTRINSIC_GUESS
+};
+
+// what cv::stereoCalibrate does not return: as CalibInfo, and camera 1's pose of every view
+struct StereoCalibInfo {
+    int status = 0, iterations = 0, trials = 0;
+    std::vector<Vec3d> rvecs, tvecs;
+    double deviceMs = 0;
+};
+
+/*
+ *   double stereoCalibrate(InputArrayOfArrays objectPoints, InputArrayOfArrays imagePoints1,
+ *                          InputArrayOfArrays imagePoints2, InputOutputArray cameraMatrix1, InputOutputArray distCoeffs1,
+ *                          InputOutputArray cameraMatrix2, InputOutputArray distCoeffs2, Size imageSize,
+ *                          InputOutputArray R, InputOutputArray T, OutputArray E, OutputArray F, int flags = CALIB_FIX_INTRINSIC,
+ *                          TermCriteria criteria = TermCriteria(COUNT + EPS, 30, 1e-6));
+ *
+ * over mcc_stereo_calibrate: camera 2 sees a view at R R_v, R t_v + T.  perViewErrors (may be null) gets each view's
+ * RMS in camera 1 and camera 2, as OpenCV's overload with perViewErrors does.  The result is the least-squares
+ * minimum of both cameras' reprojection error under the flags; bit parity with OpenCV is not claimed.
+ * Throws as calibrateCamera does.
+ */
+double stereoCalibrate(const std::vector<std::vector<Vec3d>>& objectPoints,
+                       const std::vector<std::vector<Vec2d>>& imagePoints1,
+                       const std::vector<std::vector<Vec2d>>& imagePoints2, std::array<double, 9>& cameraMatrix1,
+                       std::vector<double>& distCoeffs1, std::array<double, 9>& cameraMatrix2,
+                       std::vector<double>& distCoeffs2, Size imageSize, std::array<double, 9>& R, Vec3d& T,
+                       std::array<double, 9>& E, std::array<double, 9>& F, int flags = CALIB_FIX_INTRINSIC,
+                       TermCriteria criteria = TermCriteria(TermCriteria::COUNT + TermCriteria::EPS, 30, 1e-6),
+                       std::vector<std::array<double, 2>>* perViewErrors = nullptr, StereoCalibInfo* info = nullptr,
+                       int device = 0);
 
 }  // namespace calib
 }  // namespace mcc

@@ -95,6 +95,16 @@ CV_CALIB_USE_INTRINSIC_GUESS, CV_CALIB_FIX_ASPECT_RATIO, CV_CALIB_FIX_PRINCIPAL_
 CV_CALIB_FIX_FOCAL_LENGTH, CV_CALIB_FIX_K1, CV_CALIB_FIX_K2, CV_CALIB_FIX_K3 = 16, 32, 64, 128
 CV_CALIB_FIX_K4, CV_CALIB_FIX_K5, CV_CALIB_FIX_K6, CV_CALIB_RATIONAL_MODEL = 2048, 4096, 8192, 16384
 CALIB_CONVERGED, CALIB_COUNT, CALIB_STALLED = 0, 1, 2
+# cv::stereoCalibrate's own (mcc_stereo_calibrate)
+CV_CALIB_FIX_INTRINSIC, CV_CALIB_SAME_FOCAL_LENGTH, CV_CALIB_USE_EXTRINSIC_GUESS = 256, 512, 1 << 22
+
+
+class _StereoCalibDesc(ctypes.Structure):
+    _fields_ = [("n_views", ctypes.c_int), ("view_off", _i32p), ("obj", _f64p), ("img1", _f64p), ("img2", _f64p),
+                ("image_width", ctypes.c_int), ("image_height", ctypes.c_int), ("flags", ctypes.c_int),
+                ("nd", ctypes.c_int), ("crit_type", ctypes.c_int), ("max_count", ctypes.c_int), ("eps", ctypes.c_double),
+                ("device", ctypes.c_int), ("trials", _i32p)]
+
 
 _LIB = None
 
@@ -236,7 +246,11 @@ def lib():
                 ("mcc_calib_mask", [ctypes.c_int, ctypes.c_int, _i32p]),
                 ("mcc_init_camera_matrix", [ctypes.POINTER(_CalibDesc), ctypes.c_double, _f64p]),
                 ("mcc_calibrate_camera", [ctypes.POINTER(_CalibDesc), _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p,
-                                          _i32p, _f64p])):
+                                          _i32p, _f64p]),
+                ("mcc_stereo_calib_mask", [ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
+                ("mcc_stereo_init_extrinsics", [ctypes.c_int] + [_f64p] * 6),
+                ("mcc_stereo_epipolar", [_f64p] * 6),
+                ("mcc_stereo_calibrate", [ctypes.POINTER(_StereoCalibDesc)] + [_f64p] * 12 + [_i32p, _i32p, _f64p])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
         for name in ("mcc_omnirect_destroy", "mcc_omnirecon_destroy"):
@@ -366,6 +380,83 @@ def calibrate_camera(off, obj, img, image_size, K=None, D=None, flags=0, nd=5, m
                                       _ptr(tvec, _f64p), _ptr(vrms, _f64p), _ptr(rms, _f64p), _ptr(it, _i32p),
                                       _ptr(st, _i32p), _ptr(ms, _f64p)), "mcc_calibrate_camera")
     out = (float(rms[0]), Kio, Dio[:int(nd)], rvec, tvec, vrms, int(it[0]), int(st[0]))
+    return out + (float(ms[0]), int(tr[0])) if return_ms else out
+
+
+def stereo_calib_mask(flags=CV_CALIB_FIX_INTRINSIC, nd=5):
+    """(mask [30], tie [30]) of cv::stereoCalibrate's flags over the slots om T | camera 1's fx fy cx cy k1 k2 p1 p2
+    k3 k4 k5 k6 | camera 2's (mcc_stereo_calib_mask): mask is 1 at a free slot, tie[k] the slot that slot k follows
+    (-1: none)."""
+    m, t = np.zeros(30, np.int32), np.zeros(30, np.int32)
+    _check(lib().mcc_stereo_calib_mask(int(flags), int(nd), _ptr(m, _i32p), _ptr(t, _i32p)), "mcc_stereo_calib_mask")
+    return m, t
+
+
+def stereo_init_extrinsics(rvec1, tvec1, rvec2, tvec2):
+    """The rig's start (om [3], T [3]) from both cameras' poses of every view, [V, 3] each: cv::stereoCalibrate's
+    component-wise median (mcc_stereo_init_extrinsics).  Host only."""
+    a = [np.ascontiguousarray(x, np.float64).reshape(-1, 3) for x in (rvec1, tvec1, rvec2, tvec2)]
+    if len({len(x) for x in a}) != 1:
+        raise MccError("stereo_init_extrinsics: the four pose arrays differ in length")
+    om, T = np.zeros(3), np.zeros(3)
+    _check(lib().mcc_stereo_init_extrinsics(len(a[0]), *[_ptr(x, _f64p) for x in a], _ptr(om, _f64p), _ptr(T, _f64p)),
+           "mcc_stereo_init_extrinsics")
+    return om, T
+
+
+def stereo_epipolar(R, T, K1, K2):
+    """(E, F) of a rig as stereo_calibrate returns them: E = [T]x R, F = K2^-T E K1^-1 scaled to F[2, 2] = 1
+    (mcc_stereo_epipolar).  Host only."""
+    a = [np.ascontiguousarray(x, np.float64).reshape(n) for x, n in ((R, 9), (T, 3), (K1, 9), (K2, 9))]
+    E, F = np.zeros((3, 3)), np.zeros((3, 3))
+    _check(lib().mcc_stereo_epipolar(*[_ptr(x, _f64p) for x in a], _ptr(E, _f64p), _ptr(F, _f64p)), "mcc_stereo_epipolar")
+    return E, F
+
+
+def stereo_calibrate(off, obj, img1, img2, image_size, K1=None, D1=None, K2=None, D2=None, R=None, T=None,
+                     flags=CV_CALIB_FIX_INTRINSIC, nd=5, max_count=30, eps=1e-6, crit_type=MCC_CRIT_COUNT_EPS, device=0,
+                     return_ms=False):
+    """cv::stereoCalibrate for a pinhole pair on the GPU (mcc_stereo_calibrate): view v owns corners
+    off[v]:off[v + 1] of obj [corners, 3], img1 and img2 [corners, 2] (pixels); flags are cv::CALIB_*'s (CV_CALIB_*
+    above); nd in {4, 5, 8}.  K1 D1 K2 D2 are the intrinsics with CV_CALIB_FIX_INTRINSIC (the default) or the guess
+    with CV_CALIB_USE_INTRINSIC_GUESS; R [3, 3] and T [3] are the rig's start with CV_CALIB_USE_EXTRINSIC_GUESS.
+    Returns (rms, K1, D1, K2, D2, R, T, E, F, rvec [V, 3], tvec [V, 3], view_rms [V, 2], iterations, status): camera
+    2 sees view v at R R_v, R t_v + T; rvec, tvec are the views' poses in camera 1; status CALIB_CONVERGED,
+    CALIB_COUNT or CALIB_STALLED.  With return_ms the loop's device milliseconds and its number of trials are
+    appended."""
+    off = np.ascontiguousarray(off, np.int32).reshape(-1)
+    obj = np.ascontiguousarray(obj, np.float64).reshape(-1, 3)
+    img1 = np.ascontiguousarray(img1, np.float64).reshape(-1, 2)
+    img2 = np.ascontiguousarray(img2, np.float64).reshape(-1, 2)
+    n_views = len(off) - 1
+    if n_views >= 1 and min(len(obj), len(img1), len(img2)) < off[-1]:
+        raise MccError(f"stereo_calibrate: off names {off[-1]} corners, obj has {len(obj)}, img1 {len(img1)} and img2 {len(img2)}")
+    tr = np.zeros(1, np.int32)
+    d = _StereoCalibDesc(n_views, _ptr(off, _i32p), _ptr(obj, _f64p), _ptr(img1, _f64p), _ptr(img2, _f64p),
+                         int(image_size[0]), int(image_size[1]), int(flags), int(nd), int(crit_type), int(max_count),
+                         float(eps), int(device), _ptr(tr, _i32p))
+
+    def _D(D):
+        out = np.zeros(max(int(nd), 1))
+        if D is not None:
+            Din = np.asarray(D, np.float64).reshape(-1)
+            out[:min(len(Din), len(out))] = Din[:len(out)]
+        return out
+
+    Ks = [np.zeros((3, 3)) if K is None else np.array(K, np.float64).reshape(3, 3) for K in (K1, K2)]
+    Ds = [_D(D1), _D(D2)]
+    Rio = np.eye(3) if R is None else np.array(R, np.float64).reshape(3, 3)
+    Tio = np.zeros(3) if T is None else np.array(T, np.float64).reshape(3)
+    E, F = np.zeros((3, 3)), np.zeros((3, 3))
+    nv = max(n_views, 1)
+    rvec, tvec, vrms = np.zeros((nv, 3)), np.zeros((nv, 3)), np.zeros((nv, 2))
+    rms, ms, it, st = np.zeros(1), np.zeros(1), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    _check(lib().mcc_stereo_calibrate(ctypes.byref(d), _ptr(Ks[0], _f64p), _ptr(Ds[0], _f64p), _ptr(Ks[1], _f64p),
+                                      _ptr(Ds[1], _f64p), _ptr(Rio, _f64p), _ptr(Tio, _f64p), _ptr(E, _f64p), _ptr(F, _f64p),
+                                      _ptr(rvec, _f64p), _ptr(tvec, _f64p), _ptr(vrms, _f64p), _ptr(rms, _f64p),
+                                      _ptr(it, _i32p), _ptr(st, _i32p), _ptr(ms, _f64p)), "mcc_stereo_calibrate")
+    out = (float(rms[0]), Ks[0], Ds[0][:int(nd)], Ks[1], Ds[1][:int(nd)], Rio, Tio, E, F, rvec, tvec, vrms, int(it[0]),
+           int(st[0]))
     return out + (float(ms[0]), int(tr[0])) if return_ms else out
 
 

@@ -157,6 +157,92 @@ MCC_PNP_FN void pc_linearize(const double* obj, const double* img, int n, const 
     }
 }
 
+// pc_linearize's three passes at (cam, R, t) with the rotation columns of the pose rows taken through Jl:
+// the identity gives rows in the left tangent of R, which is what a pose that is a product needs
+// (mcc_pinstereo_device.hpp's second camera).  pc_linearize itself stays as it is, so that its results do.
+MCC_PNP_FN void pc_linearize_rj(const double* obj, const double* img, int n, const PnpCam& cam, int mask, double aspect,
+                                const double* R, const double* Jl, const double* t, int lane, double* L) {
+    {   // pass 1: U and g_pose
+        double H[21], g[6];
+#pragma unroll
+        for (int k = 0; k < 21; ++k) H[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) g[k] = 0.0;
+        for (int i = lane; i < n; i += MCC_PNP_LANES) {
+            const double X[3] = {obj[3 * i], obj[3 * i + 1], obj[3 * i + 2]};
+            double ju[6], jv[6], eu, ev;
+            pnp_rows(cam, R, Jl, t, X, img[2 * i], img[2 * i + 1], ju, jv, eu, ev);
+            int k = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                g[a] += ju[a] * eu + jv[a] * ev;
+#pragma unroll
+                for (int b = a; b < 6; ++b) H[k++] += ju[a] * ju[b] + jv[a] * jv[b];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 21; ++k) {
+            const double s = pnp_wave_sum(H[k]);
+            if (lane == 0) L[PcLin::U + k] = s;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const double s = pnp_wave_sum(g[k]);
+            if (lane == 0) L[PcLin::Gp + k] = s;
+        }
+    }
+    {   // pass 2: W
+        double W[72];
+#pragma unroll
+        for (int k = 0; k < 72; ++k) W[k] = 0.0;
+        for (int i = lane; i < n; i += MCC_PNP_LANES) {
+            const double X[3] = {obj[3 * i], obj[3 * i + 1], obj[3 * i + 2]};
+            double ju[6], jv[6], iu[kPcG], iv[kPcG], eu, ev;
+            pnp_rows(cam, R, Jl, t, X, img[2 * i], img[2 * i + 1], ju, jv, eu, ev);
+            pc_glob_rows(cam, R, t, X, mask, aspect, iu, iv);
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int j = 0; j < kPcG; ++j) W[a * kPcG + j] += ju[a] * iu[j] + jv[a] * iv[j];
+        }
+#pragma unroll
+        for (int k = 0; k < 72; ++k) {
+            const double s = pnp_wave_sum(W[k]);
+            if (lane == 0) L[PcLin::W + k] = s;
+        }
+    }
+    {   // pass 3: V and g_glob
+        double V[78], g[kPcG];
+#pragma unroll
+        for (int k = 0; k < 78; ++k) V[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < kPcG; ++k) g[k] = 0.0;
+        for (int i = lane; i < n; i += MCC_PNP_LANES) {
+            const double X[3] = {obj[3 * i], obj[3 * i + 1], obj[3 * i + 2]};
+            double ju[6], jv[6], iu[kPcG], iv[kPcG], eu, ev;
+            pnp_rows(cam, R, Jl, t, X, img[2 * i], img[2 * i + 1], ju, jv, eu, ev);
+            pc_glob_rows(cam, R, t, X, mask, aspect, iu, iv);
+            int k = 0;
+#pragma unroll
+            for (int a = 0; a < kPcG; ++a) {
+                g[a] += iu[a] * eu + iv[a] * ev;
+#pragma unroll
+                for (int b = a; b < kPcG; ++b) V[k++] += iu[a] * iu[b] + iv[a] * iv[b];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 78; ++k) {
+            const double s = pnp_wave_sum(V[k]);
+            if (lane == 0) L[PcLin::V + k] = s;
+        }
+#pragma unroll
+        for (int k = 0; k < kPcG; ++k) {
+            const double s = pnp_wave_sum(g[k]);
+            if (lane == 0) L[PcLin::Gc + k] = s;
+        }
+    }
+}
+
 // U^ [Y z] = [W g_pose] and the view's contribution.  L [PcLin::N], Yz [78] (Y [6][12], then z [6]) and
 // ctr [PcCtr::N] in LDS.  False (on every lane) when a pivot of U^ is not positive; the outputs are
 // then meaningless but written, so the reduction's tickets still complete.

@@ -99,5 +99,59 @@ std::array<double, 9> initCameraMatrix2D(const std::vector<std::vector<Vec3d>>& 
     return K;
 }
 
+double stereoCalibrate(const std::vector<std::vector<Vec3d>>& objectPoints,
+                       const std::vector<std::vector<Vec2d>>& imagePoints1,
+                       const std::vector<std::vector<Vec2d>>& imagePoints2, std::array<double, 9>& cameraMatrix1,
+                       std::vector<double>& distCoeffs1, std::array<double, 9>& cameraMatrix2,
+                       std::vector<double>& distCoeffs2, Size imageSize, std::array<double, 9>& R, Vec3d& T,
+                       std::array<double, 9>& E, std::array<double, 9>& F, int flags, TermCriteria criteria,
+                       std::vector<std::array<double, 2>>* perViewErrors, StereoCalibInfo* info, int device) {
+    const Flat f1 = flatten("stereoCalibrate", objectPoints, imagePoints1);
+    const Flat f2 = flatten("stereoCalibrate", objectPoints, imagePoints2);
+    mcc_stereo_calib_desc d{};
+    d.n_views = (int)f1.off.size() - 1;
+    d.view_off = f1.off.data();
+    d.obj = f1.obj.data();
+    d.img1 = f1.img.data();
+    d.img2 = f2.img.data();
+    d.image_width = imageSize.width;
+    d.image_height = imageSize.height;
+    d.flags = flags;
+    d.nd = (flags & CALIB_RATIONAL_MODEL) ? 8 : 5;
+    d.crit_type = criteria.type;
+    d.max_count = criteria.maxCount;
+    d.eps = criteria.epsilon;
+    d.device = device;
+    distCoeffs1.resize((size_t)d.nd, 0.0);
+    distCoeffs2.resize((size_t)d.nd, 0.0);
+    const size_t n = (size_t)d.n_views;
+    std::vector<double> r(3 * n), t(3 * n), vr(2 * n);
+    double rms = 0, ms = 0;
+    int iters = 0, status = 0, trials = 0;
+    d.trials = &trials;
+    const int rc = mcc_stereo_calibrate(&d, cameraMatrix1.data(), distCoeffs1.data(), cameraMatrix2.data(), distCoeffs2.data(),
+                                        R.data(), T.data(), E.data(), F.data(), r.data(), t.data(), vr.data(), &rms, &iters,
+                                        &status, &ms);
+    if (rc != MCC_OK) throw std::runtime_error(std::string("stereoCalibrate: ") + mcc_last_error());
+    if (perViewErrors) {
+        perViewErrors->assign(n, {0.0, 0.0});
+        for (size_t i = 0; i < n; ++i) (*perViewErrors)[i] = {vr[2 * i], vr[2 * i + 1]};
+    }
+    if (info) {
+        info->status = status;
+        info->iterations = iters;
+        info->trials = trials;
+        info->deviceMs = ms;
+        info->rvecs.assign(n, Vec3d{});
+        info->tvecs.assign(n, Vec3d{});
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k) {
+                info->rvecs[i][k] = r[3 * i + k];
+                info->tvecs[i][k] = t[3 * i + k];
+            }
+    }
+    return rms;
+}
+
 }  // namespace calib
 }  // namespace mcc

@@ -1,0 +1,190 @@
+"""The pinhole stereoCalibrate's host side and its reference, without a GPU.
+
+  * tests/npstereocalib.py converges from the truth on every noisy case of stereo_calib_cases, and what it
+    resolves there (its last Gauss-Newton step, gamma at its minimum) is within stereo_calib_cases.REF_RESOLUTION,
+    the constants the GPU test's tolerances are built on; every view of every case has a solvePnP-style seed in
+    both cameras (nppnp), and every corner is inside both images;
+  * mcc_stereo_calib_mask against a Python statement of the rules, every flag and nd in {4, 5, 8};
+  * mcc_stereo_init_extrinsics against NumPy on 2, 3 and 8 views, one view flipped so that the median is not the mean;
+  * E and F on exact data (mcc_stereo_epipolar, the function mcc_stereo_calibrate ends with);
+  * every MCC_EINVAL case of mcc_stereo_calibrate: they return before any device work.
+"""
+import ctypes
+import json
+
+import numpy as np
+import pytest
+
+import calib_cases as CC
+import npcalib
+import nppnp
+import npstereocalib as NS
+import stereo_calib_cases as SC
+from multi_camera_calibration_amd import api
+
+NOISY = {x[0]: x for x in SC.noisy_cases()}
+STEP = {x[0]: x for x in SC.step_cases()}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    api.build()
+
+
+# ---------------------------------------------------------------- the cases and the reference
+@pytest.mark.parametrize("name", list(NOISY) + list(STEP))
+def test_every_view_has_a_seed_and_is_inside_both_images(name):
+    c = (NOISY.get(name) or STEP[name])[1]
+    for cam in range(2):
+        cc = c.camera(cam)
+        g = cc.g
+        K = np.array([[g[0], 0, g[2]], [0, g[1], g[3]], [0, 0, 1.0]])
+        assert np.all(cc.img > -2) and np.all(cc.img[:, 0] < SC.SIZE[0] + 1) and np.all(cc.img[:, 1] < SC.SIZE[1] + 1)
+        for v in range(c.n_views):
+            s = c.view(v)
+            r, t, rms = nppnp.refine(cc.obj[s], cc.img[s], K, g[4:12], cc.poses[v, :3], cc.poses[v, 3:])
+            assert np.isfinite(rms) and rms < 1.0, (name, cam, v, rms)
+            Z = cc.obj[s] @ npcalib.rodrigues(r).T + t
+            assert Z[:, 2].min() > 0, (name, cam, v)
+
+
+@pytest.mark.parametrize("name", list(NOISY))
+def test_reference_converges_and_resolves(name):
+    ref = SC.reference(name)
+    res = SC.resolution(ref)
+    print("FIG", json.dumps(dict(case=name, steps=ref["steps"], rms=ref["rms"], **res)))
+    assert ref["steps"] <= 50, (name, "the reference did not converge")
+    if name == "rational":
+        # exact data: the minimum is the truth, and the reference is there when its rms is at rounding level
+        assert ref["rms"] < 1e-9
+        return
+    for k, v in res.items():
+        assert v <= SC.REF_RESOLUTION[k], (name, k, v)
+
+
+# ---------------------------------------------------------------- mcc_stereo_calib_mask
+FLAGS = [0, SC.USE_GUESS, SC.FIX_ASPECT, SC.FIX_PP, SC.ZERO_TANGENT, SC.FIX_FOCAL, SC.FIX_K1, SC.FIX_K2, SC.FIX_K3, SC.FIX_K4,
+         SC.FIX_K5, SC.FIX_K6, SC.RATIONAL, SC.FIX_INTRINSIC, SC.SAME_FOCAL, SC.USE_EXTRINSIC_GUESS,
+         SC.SAME_FOCAL | SC.FIX_ASPECT, SC.SAME_FOCAL | SC.FIX_FOCAL, SC.FIX_INTRINSIC | SC.SAME_FOCAL | SC.FIX_ASPECT,
+         SC.RATIONAL | SC.FIX_K5, SC.RATIONAL | SC.SAME_FOCAL | SC.ZERO_TANGENT | SC.FIX_K3]
+
+
+@pytest.mark.parametrize("nd", [4, 5, 8])
+@pytest.mark.parametrize("flags", FLAGS)
+def test_mask_is_the_stated_rule(flags, nd):
+    m, t = api.stereo_calib_mask(flags, nd)
+    mr, tr = SC.mask_rules(flags, nd)
+    assert np.array_equal(m, mr), (flags, nd, m, mr)
+    assert np.array_equal(t, tr), (flags, nd, t, tr)
+    assert np.all(m[t >= 0] == 0)   # a slot that follows another is not free
+
+
+def test_mask_rejects_what_it_does_not_know():
+    for flags, nd in ((1 << 10, 5), (1 << 15, 5), (1 << 21, 5), (0, 6), (0, 12)):
+        with pytest.raises(api.MccError):
+            api.stereo_calib_mask(flags, nd)
+
+
+# ---------------------------------------------------------------- mcc_stereo_init_extrinsics
+@pytest.mark.parametrize("n", [2, 3, 8])
+def test_init_extrinsics_is_the_median(n):
+    c = SC.make([20] * n, seed=500 + n)
+    c1, c2 = c.camera(0), c.camera(1)
+    p1, p2 = c1.poses.copy(), c2.poses.copy()
+    # one view's second pose off by a large rotation and shift: the median ignores it (n >= 3), the mean does not
+    Rf = npcalib.rodrigues([0.3, -0.2, 0.9])
+    p2[0, :3] = SC.rotvec(Rf @ npcalib.rodrigues(p2[0, :3]))
+    p2[0, 3:] = Rf @ p2[0, 3:] + [50.0, -20.0, 10.0]
+    oms, Ts = [], []
+    for a, b in zip(p1, p2):
+        R = npcalib.rodrigues(b[:3]) @ npcalib.rodrigues(a[:3]).T
+        oms.append(SC.rotvec(R))
+        Ts.append(b[3:] - R @ a[3:])
+    om_ref, T_ref = np.median(oms, axis=0), np.median(Ts, axis=0)
+    om, T = api.stereo_init_extrinsics(p1[:, :3], p1[:, 3:], p2[:, :3], p2[:, 3:])
+    assert np.abs(om - om_ref).max() < 1e-13 and np.abs(T - T_ref).max() < 1e-10, (om - om_ref, T - T_ref)
+    if n >= 3:
+        assert np.abs(om - c.g[0:3]).max() < 1e-12 and np.abs(T - c.g[3:6]).max() < 1e-9       # the exact rig
+        assert np.abs(np.mean(oms, axis=0) - c.g[0:3]).max() > 1e-2                             # which the mean misses
+
+
+def test_init_extrinsics_near_pi_and_identity():
+    r1 = np.array([[0.1, 0.2, -0.1], [0.0, 0.0, 0.0], [0.3, 0.0, 0.1]])
+    t1 = np.array([[1.0, 2.0, 500.0]] * 3)
+    for om_true in ([0.0, 0.0, 0.0], [np.pi - 1e-7, 0.0, 0.0], [0.0, 3.0, 0.5]):
+        R = npcalib.rodrigues(om_true)
+        r2 = np.array([SC.rotvec(R @ npcalib.rodrigues(r)) for r in r1])
+        t2 = t1 @ R.T + [-120.0, 0.0, 0.0]
+        om, T = api.stereo_init_extrinsics(r1, t1, r2, t2)
+        assert np.abs(npcalib.rodrigues(om) - R).max() < 1e-9, (om_true, om)
+        assert np.abs(T - [-120.0, 0.0, 0.0]).max() < 1e-6
+
+
+# ---------------------------------------------------------------- E and F
+def test_essential_and_fundamental_on_exact_data():
+    g1, g2 = SC.G1_TRUE.copy(), SC.G2_TRUE.copy()
+    g1[4:] = 0.0      # F relates undistorted pixels
+    g2[4:] = 0.0
+    c = SC.make(CC.RAGGED, seed=611, g1=g1, g2=g2)
+    Kof = lambda g: np.array([[g[0], 0, g[2]], [0, g[1], g[3]], [0, 0, 1.0]])
+    R, T = npcalib.rodrigues(c.g[0:3]), c.g[3:6]
+    E, F = api.stereo_epipolar(R, T, Kof(g1), Kof(g2))
+    Tx = np.array([[0.0, -T[2], T[1]], [T[2], 0.0, -T[0]], [-T[1], T[0], 0.0]])
+    E_ref = Tx @ R
+    assert np.all(np.abs(E - E_ref) <= 4 * np.spacing(np.abs(Tx).max() * np.abs(R).max())), E - E_ref
+    F_ref = NS.fundamental(c.g)
+    assert F[2, 2] == 1.0
+    h = lambda p: np.hstack([p, np.ones((len(p), 1))])
+    ep = np.abs(np.einsum("ni,ij,nj->n", h(c.img2), F, h(c.img1)))
+    ep_ref = np.abs(np.einsum("ni,ij,nj->n", h(c.img2), F_ref, h(c.img1)))
+    print("FIG", json.dumps(dict(epipolar_max=float(ep.max()), epipolar_ref_max=float(ep_ref.max()))))
+    # rounding level: the terms of x2^T F x1 are near |F| |x|^2 ~ 1, so both are a few 1e-16 .. 1e-13; the library's F is
+    # held to the same residual as NumPy's own (10 x, plus the spacing of those terms)
+    assert ep.max() <= 10 * ep_ref.max() + 1e-12
+    assert np.abs(F - F_ref).max() <= 1e-12 * np.abs(F_ref).max()
+
+
+# ---------------------------------------------------------------- MCC_EINVAL before any device work
+def _call(c, **kw):
+    a = dict(K1=CC.guess_KD(c.g[6:18], 5)[0], D1=c.g[10:15], K2=CC.guess_KD(c.g[18:30], 5)[0], D2=c.g[22:27])
+    a.update(kw)
+    return api.stereo_calibrate(c.off, c.obj, c.img1, c.img2, SC.SIZE, **a)
+
+
+def test_argument_errors():
+    c = SC.make([20] * 3, seed=700)
+    L = api.lib()
+    bad = [dict(nd=6), dict(nd=12), dict(flags=1 << 10), dict(flags=api.CV_CALIB_FIX_INTRINSIC | (1 << 20)),
+           dict(flags=api.CV_CALIB_FIX_INTRINSIC, K1=np.zeros((3, 3))), dict(flags=api.CV_CALIB_FIX_INTRINSIC, K2=np.zeros((3, 3))),
+           dict(flags=api.CV_CALIB_FIX_ASPECT_RATIO, K1=np.zeros((3, 3))), dict(crit_type=0), dict(max_count=0)]
+    for kw in bad:
+        with pytest.raises(api.MccError, match=r"\(-1\)"):
+            _call(c, **kw)
+    # a view with 3 corners, one with 1025, no views
+    for off, n in (([0, 3, 23], 23), ([0, 1025], 1025), ([0], 0)):
+        with pytest.raises(api.MccError, match=r"\(-1\)"):
+            api.stereo_calibrate(np.array(off, np.int32), np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 2)),
+                                 np.zeros((max(n, 1), 2)), SC.SIZE, K1=np.eye(3), K2=np.eye(3))
+    # null pointers
+    off = np.ascontiguousarray(c.off, np.int32)
+    K, D = np.eye(3), np.zeros(5)
+    f64 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    d = api._StereoCalibDesc(c.n_views, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), f64(c.obj), f64(c.img1), f64(c.img2),
+                             1280, 960, api.CV_CALIB_FIX_INTRINSIC, 5, 3, 30, 1e-6, 0, None)
+    outs = [None] * 11
+    assert L.mcc_stereo_calibrate(None, f64(K), f64(D), f64(K), f64(D), *outs) == -1
+    for k in range(4):
+        a = [f64(K), f64(D), f64(K), f64(D)]
+        a[k] = None
+        assert L.mcc_stereo_calibrate(ctypes.byref(d), *a, *outs) == -1
+    for field in ("view_off", "obj", "img1", "img2"):
+        d2 = api._StereoCalibDesc.from_buffer_copy(d)
+        setattr(d2, field, None)
+        assert L.mcc_stereo_calibrate(ctypes.byref(d2), f64(K), f64(D), f64(K), f64(D), *outs) == -1
+    d.flags = api.CV_CALIB_FIX_INTRINSIC | api.CV_CALIB_USE_EXTRINSIC_GUESS      # the guess without R, T
+    assert L.mcc_stereo_calibrate(ctypes.byref(d), f64(K), f64(D), f64(K), f64(D), *outs) == -1
+    assert b"stereo_calibrate" in L.mcc_last_error()
+    m = np.zeros(30, np.int32)
+    assert L.mcc_stereo_calib_mask(0, 5, None, m.ctypes.data_as(ctypes.POINTER(ctypes.c_int))) == -1
+    assert L.mcc_stereo_init_extrinsics(0, f64(D), f64(D), f64(D), f64(D), f64(D), f64(D)) == -1
+    assert L.mcc_stereo_init_extrinsics(1, None, f64(D), f64(D), f64(D), f64(D), f64(D)) == -1

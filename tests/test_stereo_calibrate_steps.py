@@ -1,0 +1,107 @@
+"""mcc_stereo_calibrate's Levenberg-Marquardt steps on the GPU, one by one against a dense reference.
+
+tests/test_stereo_calibrate.py asks whether the loop ends at the least-squares minimum, which Levenberg-Marquardt
+reaches by another path when U, W, V, the two maps, the fold of the tied columns, the damping, the packed
+contribution, the 30 x 30 solve, the back-substitution or the reuse of the stored arrow after a rejected trial is
+wrong.  Here every accepted step is compared with the step npstereocalib.lm_step takes from the same point.
+
+The state after k accepted steps is stereo_calibrate(max_count = k, eps = 0) with the case's flags (every case
+gives the intrinsics and the rig): two calls are bitwise equal, so the run to k + 1 passes through the run to k.
+State 0 is stereo_calib_cases.state0 and api.solve_pnp's poses of camera 1 at it.  For k = 0 .. K - 1 (K = 6), with
+the cases and the assertions of the one-lane walk (tests/test_pinstereo_step_cpu.py):
+
+  * iterations == k + 1;
+  * the rejections before step k + 1 (trials_(k+1) - trials_k - 1) equal the reference's count from the device's
+    state k; every decision has |en / err - 1| >= calib_cases.MARGIN;
+  * while the step is checked (calib_cases.step_checked), rho = |J (d_gpu - d_ref)| / |J d_ref| is within 10 x the
+    figure measured on an MI355X (MEASURED) and within 1e-6 whatever was measured;
+  * fixed slots are bitwise unchanged and tied slots exactly tied;
+  * every view's squared error in each camera equals npstereocalib's at the returned parameters (1e-12 relative,
+    or one spacing of a 1280 px coordinate on the view's rms where that is more).
+
+At least the first four accepted steps of each case are checked.
+"""
+import json
+
+import numpy as np
+import pytest
+
+import calib_cases as CC
+import npstereocalib as NS
+import stereo_calib_cases as SC
+from multi_camera_calibration_amd import api
+from test_pinstereo_step_cpu import check_trial
+
+pytestmark = pytest.mark.gpu
+
+CASES = {x[0]: x for x in SC.step_cases()}
+RHO_CEILING = 1e-6
+
+# the largest rho over the checked steps, measured on an MI355X
+MEASURED = {
+    "ragged9/far": 8.64e-13,
+    "17x65/aspect_same": 5.48e-11,
+    "5x20/fix_intrinsic_nd4": 7.07e-15,
+    "65x4/pp": 4.34e-11,
+}
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_every_step_is_the_reference_step(name):
+    _, c, flags, nd, guess1, guess2, rig = CASES[name]
+    mask = api.stereo_calib_mask(flags, nd)[0]
+    g, ties = SC.state0(flags, nd, guess1, guess2, rig)
+    K1, D1 = SC.guess_KD(guess1, nd)
+    K2, D2 = SC.guess_KD(guess2, nd)
+    R, T = SC.rig_RT(rig)
+    r, t, _, st = api.solve_pnp(c.obj, c.img1, c.off, np.array([[g[6], 0, g[8]], [0, g[7], g[9]], [0, 0, 1.0]]), g[10:18], max_iter=50)
+    assert np.all(st == api.PNP_SOLVED)
+    poses, trials, lam, recs, fails = np.hstack([r, t]), 0, 1e-3, [], []
+    n = np.diff(c.off)[:, None]
+    err = NS.rms(c, g, poses) ** 2 * 2 * len(c.obj)
+    for k in range(SC.K_STEPS):
+        res = api.stereo_calibrate(c.off, c.obj, c.img1, c.img2, SC.SIZE, K1=K1, D1=D1, K2=K2, D2=D2, R=R, T=T, flags=flags, nd=nd,
+                                   max_count=k + 1, eps=0.0, return_ms=True)
+        assert res[12] == k + 1 and res[13] == api.CALIB_COUNT, (name, k, res[12], res[13])
+        g1 = SC.globals_of(res[1], res[2], res[3], res[4], res[5], res[6])
+        if flags & SC.FIX_INTRINSIC:
+            g1[6:30] = g[6:30]            # (the slots past nd, which the call does not return)
+        poses1 = np.hstack([res[9], res[10]])
+        rej = res[15] - trials - 1
+        j, _, ratios = NS.lm_rejections(c, g, poses, mask, lam, ties)
+        lam_used = lam
+        for _ in range(rej):
+            lam_used = lam_used * 10.0
+        en = res[0] ** 2 * 2 * len(c.obj)
+        trial = dict(ok=True, err=err, en=en, g=g1, x=poses1, sq=res[11] ** 2 * n)
+        rec, _ = check_trial(c, trial, g, poses, mask, ties, lam_used, None, None, k)
+        rec.update(rejections=int(rej), ref_rejections=j, ratios=ratios)
+        print("FIG", json.dumps({"case": name, **{q: rec[q] for q in ("step", "lam", "gamma", "rms", "ratio", "ref_ratio", "rho",
+                                                                      "dview", "rejections", "ref_rejections", "ratios")}}))
+        recs.append(rec)
+        checked = CC.step_checked(rec["gamma"], rec["rms"])
+        if rej != j:
+            fails.append((k, "rejections", int(rej), j))
+        if not all(abs(q - 1.0) >= CC.MARGIN for q in ratios) or abs(rec["ratio"] - 1.0) < CC.MARGIN:
+            fails.append((k, "a decision inside the margin", ratios, rec["ratio"]))
+        if checked and not rec["rho"] <= min(10.0 * MEASURED.get(name, 0.0), RHO_CEILING):
+            fails.append((k, "rho", rec["rho"]))
+        a1, a2, same = ties
+        followers = [6] * (a1 > 0) + [18] * (a2 > 0 or bool(same)) + [19] * bool(same)
+        fixed = [q for q in range(30) if not mask[q] and q not in followers]
+        if not np.array_equal(g1[fixed], g[fixed]):
+            fails.append((k, "a fixed slot moved", g1[fixed] - g[fixed]))
+        if a1 > 0 and g1[6] != a1 * g1[7]:
+            fails.append((k, "fx1 != a fy1"))
+        if same and (g1[19] != g1[7] or g1[18] != (a2 * g1[19] if a2 > 0 else g1[6])):
+            fails.append((k, "camera 2's focal lengths do not follow camera 1's"))
+        if not rec["view_ok"]:
+            fails.append((k, "view_rms", rec["dview"]))
+        g, poses, trials, err = g1, poses1, res[15], en
+        lam = max(lam_used * 0.1, 1e-12)
+    checked = [q for q in recs if CC.step_checked(q["gamma"], q["rms"])]
+    print("FIG", json.dumps(dict(case=name, checked=len(checked), rho_max=max(q["rho"] for q in checked))))
+    assert not fails, fails
+    assert all(CC.step_checked(q["gamma"], q["rms"]) for q in recs[:SC.MIN_CHECKED])
+    if name == "ragged9/far":
+        assert any(q["rejections"] > 0 and CC.step_checked(q["gamma"], q["rms"]) and q["step"] > 0 for q in recs)
