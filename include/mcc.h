@@ -378,7 +378,9 @@ int mcc_stereo_calib_mask(int flags, int nd, int *mask /* [30] */, int *tie /* [
 
 /* The rig's start from both cameras' poses of every view (rvec, tvec [3*n_views] each), cv::stereoCalibrate's
  * rule: the component-wise median over the views of the rotation vector of R_2v R_1v^T and of
- * t_2v - R_2v R_1v^T t_1v (the middle value, or the mean of the middle two).  Host only. */
+ * t_2v - R_2v R_1v^T t_1v (the middle value, or the mean of the middle two).  Near a half turn the views' vectors
+ * are first moved to one side of pi (r and r (1 - 2 pi / |r|) are the same rotation), so |om| may exceed pi; away
+ * from it the result is the plain median.  Host only. */
 int mcc_stereo_init_extrinsics(int n_views, const double *rvec1, const double *tvec1, const double *rvec2,
                                const double *tvec2, double *om /* [3] */, double *T /* [3] */);
 

@@ -92,6 +92,44 @@ double median(std::vector<double> a) {
     return n % 2 ? a[n / 2] : 0.5 * (a[n / 2 - 1] + a[n / 2]);
 }
 
+// r and r (1 - 2 pi / |r|) are the same rotation.  Within noise of a half turn some views' logarithms come out on
+// one side of pi and some on the other, and a component-wise median over both is near 0.  So every view's vector
+// is replaced by whichever of its two forms is nearer to a reference view's: the view that asks the fewest others
+// to change (the first of equals), which one outlier cannot be unless n = 2.  Away from a half turn nobody changes
+// and the columns are what log_host gave.
+void same_side_of_pi(int n, std::vector<double>* col) {
+    auto alt = [&](int v, double* a) {
+        const double th = std::sqrt(col[0][v] * col[0][v] + col[1][v] * col[1][v] + col[2][v] * col[2][v]);
+        if (!(th > 0)) return false;
+        const double k = 1.0 - 2.0 * M_PI / th;
+        for (int i = 0; i < 3; ++i) a[i] = k * col[i][v];
+        return true;
+    };
+    auto nearer = [&](int v, int ref, double* a) {   // is view v's other form nearer to ref's vector than its own?
+        if (v == ref || !alt(v, a)) return false;
+        double d0 = 0, d1 = 0;
+        for (int i = 0; i < 3; ++i) {
+            d0 += (col[i][v] - col[i][ref]) * (col[i][v] - col[i][ref]);
+            d1 += (a[i] - col[i][ref]) * (a[i] - col[i][ref]);
+        }
+        return d1 < d0;
+    };
+    double a[3];
+    int ref = 0, fewest = n + 1;
+    for (int c = 0; c < n && fewest > 0; ++c) {
+        int changes = 0;
+        for (int v = 0; v < n; ++v) changes += nearer(v, c, a);
+        if (changes < fewest) {
+            fewest = changes;
+            ref = c;
+        }
+    }
+    if (fewest == 0) return;
+    for (int v = 0; v < n; ++v)   // (the reference's own vector stays, so every view is compared with the same one)
+        if (nearer(v, ref, a))
+            for (int i = 0; i < 3; ++i) col[i][v] = a[i];
+}
+
 void init_extrinsics(int n, const double* r1, const double* t1, const double* r2, const double* t2, double* om, double* T) {
     std::vector<double> col[6];
     for (int v = 0; v < n; ++v) {
@@ -108,6 +146,7 @@ void init_extrinsics(int n, const double* r1, const double* t1, const double* r2
             col[3 + k].push_back(t2[3 * (size_t)v + k] - (R[k * 3] * a[0] + R[k * 3 + 1] * a[1] + R[k * 3 + 2] * a[2]));
         }
     }
+    same_side_of_pi(n, col);
     for (int k = 0; k < 3; ++k) {
         om[k] = median(col[k]);
         T[k] = median(col[3 + k]);

@@ -54,14 +54,16 @@ def grid(n, relief=0.0):
     return X.astype(np.float64)
 
 
-def make(corners, seed, noise=0.0, relief=0.0, g=G_TRUE):
-    """One view per entry of `corners`."""
+def make(corners, seed, noise=0.0, relief=0.0, g=G_TRUE, view_r=None):
+    """One view per entry of `corners`.  view_r: {view: rotation vector} for views whose rotation is prescribed."""
     rng = np.random.default_rng(seed)
     obj, img, poses, off = [], [], [], [0]
     for v, n in enumerate(corners):
         tilt = np.deg2rad(rng.uniform(10.0, 45.0))
         phi = 2.399963 * v + rng.uniform(0.0, 0.5)   # the golden angle: axes spread over the circle
         r = np.array([tilt * np.cos(phi), tilt * np.sin(phi), rng.uniform(-0.3, 0.3)])
+        if view_r and v in view_r:
+            r = np.asarray(view_r[v], np.float64)
         t = np.array([rng.uniform(-60.0, 60.0), rng.uniform(-40.0, 40.0), rng.uniform(500.0, 1200.0)])
         X = grid(n, relief)
         obj.append(X)
@@ -108,6 +110,9 @@ def noisy_cases():
     return out
 
 
+NEAR_ZERO_VIEW = 2
+
+
 def step_cases():
     """(name, case, flags, nd, guess) of tests/test_calibrate_camera_steps.py and tests/test_pincalib_step_cpu.py:
     the smallest inputs whose Levenberg-Marquardt trajectory from the guess reaches each path of the trial
@@ -122,11 +127,15 @@ def step_cases():
     #                                   decision is no longer clear (MARGIN); from here all six steps are far from it
     rat = make([88] * 10, seed=310, g=G_RATIONAL)      # exact: k4 .. k6 are not determined under noise
     four = make([4] * 65, seed=465, noise=0.2)         # groups of 9 views, the last of 2
+    # one view almost parallel to the image plane: k_pc_lin's only run of so3_jac's series (|r_v| < 1e-2).  The draw
+    # (of 40 tried) on which that view stays under 1e-2 on all six steps; 20 noisy corners hold its tilt to 2e-2 only
+    nzv = make([20] * 5, seed=612, noise=0.2, view_r={NEAR_ZERO_VIEW: np.random.default_rng(613).normal(0.0, 2e-3, 3)})
     return [("ragged9/far", far, USE_GUESS, 5, g_far),
             ("17x65/aspect", asp, USE_GUESS | FIX_ASPECT, 5, asp.g * 1.05),
             ("5x20/nd4_pp", nd4, USE_GUESS | FIX_PP, 4, g_nd4),
             ("10x88/rational_k5", rat, USE_GUESS | RATIONAL | FIX_K5, 8, rat.g * 1.01),
-            ("65x4", four, USE_GUESS, 5, four.g * 1.01)]
+            ("65x4", four, USE_GUESS, 5, four.g * 1.01),
+            ("5x20/near_zero_view", nzv, USE_GUESS, 5, nzv.g * 1.01)]
 
 
 # What the step tests walk and where they compare a step with npcalib.lm_step:

@@ -4,6 +4,9 @@ tests/test_pinstereo_step_cpu.py), built from calib_cases' grid and pose distrib
 Camera 1 is calib_cases.G_TRUE; camera 2 is a second intrinsic set a few percent off, 120 mm to the right of
 camera 1 and turned by about 3.5 degrees.  A view's pose is drawn as calib_cases.make draws it and drawn again
 until every corner is in front of both cameras and inside 1280 x 960 in both.
+
+RIGS, rig_cases() and rig_step_cases() are other rigs (no rotation, a toe-in, a quarter turn, one camera ahead,
+two half turns) and `poses`, views off that pose distribution; the tests on them compare rotations by rot_angle.
 """
 from __future__ import annotations
 
@@ -69,12 +72,37 @@ def rotvec(R):
     return v * (0.5 if th < 1e-12 else th / (2.0 * s))
 
 
+def rot_angle(Ra, Rb):
+    """The angle of Ra Rb^T, from atan2: good at 0 and at pi alike, and blind to which of a rotation's vectors
+    (r, or r (1 - 2 pi / |r|)) either side was made from."""
+    D = np.asarray(Ra, np.float64) @ np.asarray(Rb, np.float64).T
+    s = 0.5 * np.sqrt((D[2, 1] - D[1, 2]) ** 2 + (D[0, 2] - D[2, 0]) ** 2 + (D[1, 0] - D[0, 1]) ** 2)
+    return float(np.arctan2(s, (np.trace(D) - 1.0) * 0.5))
+
+
+def log_so3(R):
+    """A rotation vector of R at any angle in [0, pi]: rotvec's form while sin(angle) >= 0.1; nearer to a half turn
+    the axis from the symmetric part, (R + R^T) / 2 = c I + (1 - c) a a^T, with the sign of the skew part."""
+    R = np.asarray(R, np.float64)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = 0.5 * np.linalg.norm(v), (np.trace(R) - 1.0) * 0.5
+    if s >= 0.1 or c > 0:
+        return rotvec(R)
+    S = 0.5 * (R + R.T) - c * np.eye(3)
+    a = S[:, int(np.argmax(np.diag(S)))]
+    a = a / np.linalg.norm(a)
+    return (-a if a @ v < 0 else a) * np.arctan2(s, c)
+
+
 def _inside(p):
     return bool(np.all(p[:, 0] > 0) and np.all(p[:, 0] < SIZE[0] - 1) and np.all(p[:, 1] > 0) and np.all(p[:, 1] < SIZE[1] - 1))
 
 
-def make(corners, seed, noise=0.0, g1=G1_TRUE, g2=G2_TRUE, om=OM_TRUE, T=T_TRUE, fronto=False):
-    """One view pair per entry of `corners`.  fronto: targets parallel to camera 1's image plane."""
+def make(corners, seed, noise=0.0, g1=G1_TRUE, g2=G2_TRUE, om=OM_TRUE, T=T_TRUE, fronto=False, x_mean=60.0, view_r=None):
+    """One view pair per entry of `corners`.  fronto: targets parallel to camera 1's image plane.  x_mean: the mean x
+    (mm, camera 1) of the target's position.  view_r: {view: rotation vector, or a function of the drawn one} for
+    views whose rotation is prescribed; their position is still drawn (and drawn again) as every view's."""
+    view_r = view_r or {}
     rng = np.random.default_rng(seed)
     g = np.concatenate([om, T, g1, g2]).astype(np.float64)
     R = npcalib.rodrigues(om)
@@ -85,7 +113,9 @@ def make(corners, seed, noise=0.0, g1=G1_TRUE, g2=G2_TRUE, om=OM_TRUE, T=T_TRUE,
             tilt = 0.0 if fronto else np.deg2rad(rng.uniform(10.0, 45.0))
             phi = 2.399963 * v + rng.uniform(0.0, 0.5)
             r = np.array([tilt * np.cos(phi), tilt * np.sin(phi), 0.0 if fronto else rng.uniform(-0.3, 0.3)])
-            t = np.array([rng.uniform(-60.0, 60.0) + 60.0, rng.uniform(-40.0, 40.0), rng.uniform(500.0, 1200.0)])
+            if v in view_r:
+                r = np.asarray(view_r[v](r) if callable(view_r[v]) else view_r[v], np.float64)
+            t = np.array([rng.uniform(-60.0, 60.0) + x_mean, rng.uniform(-40.0, 40.0), rng.uniform(500.0, 1200.0)])
             pose = np.concatenate([r, t])
             p1, p2 = NS.project2(X, g, pose)
             Z1 = (X @ npcalib.rodrigues(r).T + t)
@@ -222,6 +252,109 @@ def step_cases():
             ("65x4/pp", four, USE_GUESS | E | FIX_PP, 5, four.g[6:18] * 1.01, four.g[18:30] * 1.01, rig(four, 1.05))]
 
 
+# ---------------------------------------------------------------- rigs other than the one above
+# name: (om, camera 2's centre C2 in camera 1's frame in mm, the mean x of the target's position); T = -R C2
+RIGS = {
+    "rot0": ((0.0, 0.0, 0.0), (120.0, 0.0, 0.0), 60.0),               # rodrigues_v2m's theta < eps branch, so3_jac's series
+    "series": ((3e-3, -4e-3, 2e-3), (120.0, -3.0, 5.0), 60.0),         # so3_jac's series at a generic small vector
+    "toe_in": ((0.03, 0.40, 0.02), (300.0, 5.0, 40.0), 150.0),         # a large Jl(om); R far from I in A and in [R t_v]x
+    "roll90": ((0.02, -0.03, np.pi / 2), (10.0, 150.0, 0.0), 60.0),    # x and y exchanged, the baseline along y
+    "forward": ((0.01, 0.02, -0.015), (5.0, -8.0, 150.0), 60.0),       # the baseline along z: the dT block's third column
+    "upside_down": ((0.004, -0.006, np.pi - 5e-4), (120.0, 4.0, -3.0), 60.0),                 # within noise of a half turn
+    "half_turn_tilted": (tuple(np.pi * np.array([np.sin(0.1), 0.0, np.cos(0.1)])), (200.0, 0.0, 0.0), 100.0),
+}
+HALF_TURN = ("upside_down", "half_turn_tilted")
+
+
+def rig_of(name):
+    """(om, T, x_mean) of a rig of RIGS."""
+    om, C2, x_mean = RIGS[name]
+    om = np.array(om, np.float64)
+    return om, -npcalib.rodrigues(om) @ np.array(C2, np.float64), x_mean
+
+
+def make_rig(name, corners, seed, noise=0.0, **kw):
+    om, T, x_mean = rig_of(name)
+    return make(corners, seed, noise, om=om, T=T, x_mean=x_mean, **kw)
+
+
+def exact_rig(name):
+    """Exact 5 x 20 (groups of 3 + 2 views) of a rig."""
+    return make_rig(name, [20] * 5, seed=905)
+
+
+_RIG_CASES = {}
+
+
+def rig_cases():
+    """{name: case}: noisy 17 x 88 of every rig of RIGS (seed 300, 0.2 px), upside_down once more with 16 views, and
+    `poses` (below)."""
+    if not _RIG_CASES:
+        for name in RIGS:
+            _RIG_CASES[name] = make_rig(name, [88] * 17, seed=300, noise=0.2)
+        _RIG_CASES["upside_down16"] = make_rig("upside_down", [88] * 16, seed=300, noise=0.2)
+        _RIG_CASES["poses"] = poses_case([88] * 17, seed=300)
+    return _RIG_CASES
+
+
+NEAR_ZERO_VIEW, ROLLED_VIEW = 2, 5
+ROLL = 3.1
+
+
+def rolled(r):
+    """The drawn rotation turned by ROLL about the optical axis."""
+    return log_so3(npcalib.rodrigues([0.0, 0.0, ROLL]) @ npcalib.rodrigues(r))
+
+
+def near_zero(seed):
+    """A view rotation N(0, 2e-3) per component: |r_v| under so3_jac's series threshold of 1e-2."""
+    return np.random.default_rng(seed).normal(0.0, 2e-3, 3)
+
+
+def poses_case(corners, seed, noise=0.2, **kw):
+    """The rig of the module's head with two views off calib_cases' pose distribution: view NEAR_ZERO_VIEW almost
+    parallel to camera 1's image plane, view ROLLED_VIEW rolled by 3.1 rad on top of its tilt."""
+    return make(corners, seed, noise, view_r={NEAR_ZERO_VIEW: near_zero(seed + 1), ROLLED_VIEW: rolled}, **kw)
+
+
+def rig_noisy_cases():
+    """(name, case, flags, nd, guess1, guess2, rig) in noisy_cases()' form: every case of rig_cases() with flags 0 and
+    with FIX_INTRINSIC at the true intrinsics."""
+    out = []
+    for name, c in rig_cases().items():
+        out += [(name + "/flags0", c, 0, 5, None, None, None),
+                (name + "/fix_intrinsic", c, FIX_INTRINSIC, 5, c.g[6:18], c.g[18:30], None)]
+    return out
+
+
+# What tests/npstereocalib.py resolves on rig_noisy_cases(), measured as REF_RESOLUTION was and rounded up to one digit.
+# Measured maxima over the cases: dK 1.3e-10, dD 2.4e-9 (upside_down/flags0), dom 8.6e-11 (upside_down/flags0), dT 2.0e-8
+# (toe_in/flags0), dr 1.2e-8 (toe_in/fix_intrinsic), dt 1.6e-7, gamma 7.9e-10 (upside_down16/fix_intrinsic).
+RIG_REF_RESOLUTION = dict(dK=2e-10, dD=3e-9, dom=9e-11, dT=2e-8, dr=2e-8, dt=2e-7, gamma=8e-10)
+
+
+def rig_step_cases():
+    """step_cases()' form on the rigs of RIGS: the smallest inputs on which the two maps of k_ps_lin are far from
+    what they are on the rig of the module's head."""
+    E = USE_EXTRINSIC_GUESS
+    rig = lambda c, s: np.concatenate([c.g[0:3] * s, c.g[3:6] * s])
+    toe = make_rig("toe_in", [20] * 5, seed=520, noise=0.2)                     # groups of 3 + 2 views
+    # the draw (of 39 tried) on which the 5 x 20 minimum keeps |om| and the near-zero view's |r_v| under 1e-2 all the
+    # way: 20 noisy corners hold a view's tilt and five views the rig's rotation to about 2e-2 only
+    ser = make_rig("series", [20] * 5, seed=527, noise=0.2, view_r={NEAR_ZERO_VIEW: near_zero(528)})
+    r90 = make_rig("roll90", [20] * 9, seed=523, noise=0.2)                     # groups of 3 views
+    fwd = make_rig("forward", [20] * 5, seed=524, noise=0.2)
+    return [("5x20/toe_in", toe, USE_GUESS | E, 5, toe.g[6:18] * 1.05, toe.g[18:30] * 1.05, rig(toe, 1.1)),
+            # Jl(om) and Jl(r_v) of view NEAR_ZERO_VIEW both from so3_jac's series in one trial
+            ("5x20/series_poses", ser, USE_GUESS | E, 5, ser.g[6:18] * 1.01, ser.g[18:30] * 1.01, rig(ser, 1.05)),
+            # SAME_FOCAL_LENGTH without FIX_ASPECT_RATIO: camera 2's fx follows camera 1's fx, not its own fy
+            ("9x20/roll90_same", r90, USE_GUESS | E | SAME_FOCAL, 5, r90.g[6:18] * 1.05, r90.g[18:30] * 1.05, rig(r90, 1.1)),
+            # 0.5 rad and 2 x T off, as 5x20/fix_intrinsic_nd4 is: from 0.3 rad and 1.5 x T the walk is at its minimum
+            # after four steps and the sixth decision is inside the margin (|en / err - 1| = 2e-11)
+            ("5x20/forward_fix", fwd, FIX_INTRINSIC | E, 5, fwd.g[6:18], fwd.g[18:30],
+             np.concatenate([fwd.g[0:3] + np.array([0.2, -0.15, 0.17]) * (0.5 / 0.3), fwd.g[3:6] * 2.0]))]
+
+
 _REF = {}
 
 
@@ -229,7 +362,8 @@ def reference(name):
     """tests/npstereocalib.py's minimum of a noisy case, computed once and shared: a dict with g [30], poses, rms,
     steps, last (the last Gauss-Newton step: dg, dposes), gamma at the minimum, mask and ties."""
     if name not in _REF:
-        _, c, flags, nd, guess1, guess2, _rig = {x[0]: x for x in noisy_cases()}[name]
+        table = rig_noisy_cases() if "/" in name else noisy_cases()
+        _, c, flags, nd, guess1, guess2, _rig = {x[0]: x for x in table}[name]
         mask, _ = mask_rules(flags, nd)
         K1, K2 = (guess_KD(gs, nd)[0] for gs in (guess1, guess2))
         ties = ties_of(flags, K1, K2)

@@ -28,7 +28,8 @@ bitwise equal, so the run to k + 1 passes through the run to k.  State 0 is the 
     largest coordinate a residual is formed from.  It happens to be 6 x the measurement.
 
 Each step starts from the device's own previous iterate, so nothing drifts.  At least three steps per case are
-checked.  Not covered: steps with gamma < 1e-4, the stall path, rational models under noise.
+checked.  5x20/near_zero_view has a view with |r_v| < 1e-2 on every step: k_pc_lin's run of so3_jac's series
+(tests/test_pincalib_step_cpu.py asserts that it stays there).  Not covered: steps with gamma < 1e-4, the stall path, rational models under noise.
 """
 import json
 
@@ -52,6 +53,7 @@ MEASURED = {
     "5x20/nd4_pp": 1.90e-13,
     "10x88/rational_k5": 6.49e-11,
     "65x4": 1.75e-11,
+    "5x20/near_zero_view": 2.83e-11,
 }
 
 

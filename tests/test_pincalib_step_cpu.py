@@ -104,7 +104,7 @@ def walk(exe, name):
         rec = dict(step=step, lam=lam, gamma=gam, rms=float(np.sqrt(t["err"] / len(c.obj))), ratio=t["en"] / t["err"],
                    ref_ratio=float(ref_ratio), accept=bool(accept),
                    rho=npcalib.rho(J, free, (t["g"] - g, t["x"] - poses), (dg, dp)), g0=g, g1=t["g"], aspect=aspect,
-                   mask=mask, dview=float(dview.max()), view_ok=bool(np.all(dview <= np.maximum(1e-12 * vr_ref, PIXEL_SPACING))))
+                   mask=mask, x0=poses, dview=float(dview.max()), view_ok=bool(np.all(dview <= np.maximum(1e-12 * vr_ref, PIXEL_SPACING))))
         trials.append(rec)
         if accept:
             g, poses, lam, step, tries = t["g"], t["x"], max(lam * 0.1, 1e-12), step + 1, 0
@@ -148,3 +148,11 @@ def test_inputs_of_the_gpu_step_test(exe, name):
         # relin = 0: the stored sums read again at another lambda, in a step that is checked
         assert any(not a["accept"] and b["accept"] and CC.step_checked(b["gamma"], b["rms"])
                    for a, b in zip(trials, trials[1:]))
+
+
+def test_the_near_zero_view_stays_in_the_series_branch(exe):
+    """5x20/near_zero_view is k_pc_lin's run of so3_jac's series (th < 1e-2): the view is there at every trial."""
+    trials = walk(exe, "5x20/near_zero_view")
+    rv = [float(np.linalg.norm(t["x0"][CC.NEAR_ZERO_VIEW, :3])) for t in trials]
+    print("FIG", json.dumps({"case": "5x20/near_zero_view", "rv": rv}))
+    assert max(rv) < 1e-2, rv

@@ -20,6 +20,10 @@ The same walk checks what tests/test_stereo_calibrate_steps.py needs of its inpu
 decision is clear (|en / err - 1| >= calib_cases.MARGIN) and the reference takes the same one; at least the
 first four accepted steps of each case are checked; ragged9/far has a rejection followed by an accepted,
 checked step (relin = 0: the stored arrow read again at another lambda).
+
+stereo_calib_cases.rig_step_cases() go through the same walk and assertions with their own measured figure:
+rigs on which Jl(om), its transpose and the identity, and R t_v and R^T t_v, are far apart, and one on which both
+of k_ps_lin's so3_jac calls take the series (|om| and one view's |r_v| under 1e-2, asserted on every trial).
 """
 import json
 import os
@@ -41,6 +45,11 @@ RHO_MEASURED = 6.9e-11                    # the largest rho of a checked trial h
 RHO_GATE = min(10 * RHO_MEASURED, 1e-6)
 PIXEL_SPACING = float(np.spacing(1280.0))
 CASES = {x[0]: x for x in SC.step_cases()}
+# stereo_calib_cases.rig_step_cases(): the same walk on rigs far from the identity, under the same assertions, with
+# its own measured figure (RHO_MEASURED stays what step_cases() gave)
+RIG_CASES = {x[0]: x for x in SC.rig_step_cases()}
+RIG_RHO_MEASURED = 8.8e-11                   # the largest rho of a checked trial of RIG_CASES, one lane
+RIG_RHO_GATE = min(10 * RIG_RHO_MEASURED, 1e-6)
 
 
 @pytest.fixture(scope="module")
@@ -85,12 +94,12 @@ def check_trial(c, t, g, poses, mask, ties, lam, lin, gam, step):
     rec = dict(step=step, lam=lam, gamma=gam, rms=float(np.sqrt(t["err"] / (2 * len(c.obj)))), ratio=t["en"] / t["err"],
                ref_ratio=float(ref_ratio), accept=bool(accept),
                rho=NS.rho(J, free, (t["g"] - g, t["x"] - poses), (dg, dp)), g0=g, g1=t["g"], ties=ties, mask=mask,
-               dview=float(dview.max()), view_ok=bool(np.all(dview <= np.maximum(1e-12 * vr_ref, PIXEL_SPACING))))
+               x0=poses, dview=float(dview.max()), view_ok=bool(np.all(dview <= np.maximum(1e-12 * vr_ref, PIXEL_SPACING))))
     return rec, (J, e)
 
 
 def start_of(name):
-    _, c, flags, nd, guess1, guess2, rig = CASES[name]
+    _, c, flags, nd, guess1, guess2, rig = (CASES.get(name) or RIG_CASES[name])
     mask = api.stereo_calib_mask(flags, nd)[0]
     g, ties = SC.state0(flags, nd, guess1, guess2, rig)
     return c, mask, g, ties
@@ -159,3 +168,17 @@ def test_one_lane_trial_is_the_reference_step(exe, name):
         print("FIG", json.dumps({"case": name, **{k: t[k] for k in ("step", "lam", "gamma", "rms", "accept", "ratio", "ref_ratio",
                                                                      "rho", "dview")}}))
     assert_trials(name, trials, RHO_GATE)
+
+
+@pytest.mark.parametrize("name", list(RIG_CASES))
+def test_one_lane_trial_is_the_reference_step_on_the_rigs(exe, name):
+    trials = walk(exe, name)
+    for t in trials:
+        print("FIG", json.dumps({"case": name, **{k: t[k] for k in ("step", "lam", "gamma", "rms", "accept", "ratio", "ref_ratio",
+                                                                     "rho", "dview")}}))
+    if name == "5x20/series_poses":
+        # both of k_ps_lin's so3_jac calls take the series in every trial: |om| and the near-zero view's |r_v| < 1e-2
+        small = [(float(np.linalg.norm(t["g0"][0:3])), float(np.linalg.norm(t["x0"][SC.NEAR_ZERO_VIEW, :3]))) for t in trials]
+        print("FIG", json.dumps({"case": name, "om_rv": small}))
+        assert all(a < 1e-2 and b < 1e-2 for a, b in small), small
+    assert_trials(name, trials, RIG_RHO_GATE)

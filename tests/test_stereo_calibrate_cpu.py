@@ -5,7 +5,10 @@
     the constants the GPU test's tolerances are built on; every view of every case has a solvePnP-style seed in
     both cameras (nppnp), and every corner is inside both images;
   * mcc_stereo_calib_mask against a Python statement of the rules, every flag and nd in {4, 5, 8};
+  * the same for the rigs and poses of stereo_calib_cases.RIGS / rig_cases() / rig_step_cases(), held to
+    RIG_REF_RESOLUTION, with the near-zero view of `poses` under so3_jac's series threshold at the minimum;
   * mcc_stereo_init_extrinsics against NumPy on 2, 3 and 8 views, one view flipped so that the median is not the mean;
+    at a half turn, the views' logarithms half on each side of pi; bitwise the plain median away from it;
   * E and F on exact data (mcc_stereo_epipolar, the function mcc_stereo_calibrate ends with);
   * every MCC_EINVAL case of mcc_stereo_calibrate: they return before any device work.
 """
@@ -60,6 +63,71 @@ def test_reference_converges_and_resolves(name):
         return
     for k, v in res.items():
         assert v <= SC.REF_RESOLUTION[k], (name, k, v)
+
+
+# ---------------------------------------------------------------- the rigs off the one above (stereo_calib_cases.RIGS)
+RIG = SC.rig_cases()
+RIG_NOISY = {x[0]: x for x in SC.rig_noisy_cases()}
+RIG_STEP = {x[0]: x for x in SC.rig_step_cases()}
+
+
+def test_the_existing_cases_are_the_arrays_they_were():
+    """make()'s new arguments at their defaults draw what it drew before: elements of noisy_cases()' first case."""
+    c = NOISY["flags0"][1]
+    assert np.abs(c.img2[1000] - [371.28518262, 418.81032635]).max() < 5e-9
+    assert np.abs(c.poses[16] - [2.56988490e-01, 2.43742966e-01, 2.14331334e-02, 3.76465433e+00, 1.93307703e+01,
+                                 5.80690891e+02]).max() < 5e-7
+    assert np.array_equal(c.g[0:6], np.concatenate([SC.OM_TRUE, SC.T_TRUE]))
+
+
+@pytest.mark.parametrize("name", list(RIG) + list(RIG_STEP) + ["exact/" + r for r in SC.RIGS])
+def test_every_view_of_a_rig_case_has_a_seed_and_is_inside_both_images(name):
+    c = RIG[name] if name in RIG else SC.exact_rig(name[6:]) if name.startswith("exact/") else RIG_STEP[name][1]
+    for cam in range(2):
+        g = c.g[6:18] if cam == 0 else c.g[18:30]
+        img = c.img1 if cam == 0 else c.img2
+        K = np.array([[g[0], 0, g[2]], [0, g[1], g[3]], [0, 0, 1.0]])
+        assert np.all(img > -2) and np.all(img[:, 0] < SC.SIZE[0] + 1) and np.all(img[:, 1] < SC.SIZE[1] + 1)
+        R = npcalib.rodrigues(c.g[0:3])
+        for v in range(c.n_views):
+            s = c.view(v)
+            # the view's pose in this camera, as a rotation vector at any angle (camera 2's is near pi on two rigs)
+            Rv = npcalib.rodrigues(c.poses[v, :3])
+            r0 = c.poses[v, :3] if cam == 0 else SC.log_so3(R @ Rv)
+            t0 = c.poses[v, 3:] if cam == 0 else R @ c.poses[v, 3:] + c.g[3:6]
+            r, t, rms = nppnp.refine(c.obj[s], img[s], K, g[4:12], r0, t0)
+            assert np.isfinite(rms) and rms < 1.0, (name, cam, v, rms)
+            Z = c.obj[s] @ npcalib.rodrigues(r).T + t
+            assert Z[:, 2].min() > 0, (name, cam, v)
+            assert SC.rot_angle(npcalib.rodrigues(r), npcalib.rodrigues(r0)) < 0.05, (name, cam, v)
+
+
+@pytest.mark.parametrize("name", list(RIG_NOISY))
+def test_reference_converges_and_resolves_on_the_rigs(name):
+    ref = SC.reference(name)
+    res = SC.resolution(ref)
+    c = RIG_NOISY[name][1]
+    print("FIG", json.dumps(dict(case=name, steps=ref["steps"], rms=ref["rms"], **res)))
+    assert ref["steps"] <= 50, (name, "the reference did not converge")
+    assert SC.rot_angle(npcalib.rodrigues(ref["g"][0:3]), npcalib.rodrigues(c.g[0:3])) < 5e-3     # the minimum next to the truth
+    for k, v in res.items():
+        assert v <= SC.RIG_REF_RESOLUTION[k], (name, k, v)
+    if name.startswith("poses/"):
+        nz = float(np.linalg.norm(ref["poses"][SC.NEAR_ZERO_VIEW, :3]))
+        print("FIG", json.dumps(dict(case=name, near_zero_view=nz)))
+        assert nz < 1e-2        # so3_jac's series branch, at the minimum the device is compared at
+        assert npcalib.rodrigues(c.poses[SC.ROLLED_VIEW, :3])[0, 0] < -0.9        # the target's x axis points to -x
+
+
+def test_rot_angle_and_log_so3_at_the_ends():
+    for r in ([0.0, 0.0, 0.0], [1e-9, -2e-9, 0.0], [0.3, -0.2, 0.9], [0.0, 0.0, np.pi - 5e-4], [np.pi, 0.0, 0.0],
+              list(np.pi * np.array([np.sin(0.1), 0.0, np.cos(0.1)])), [0.0, -(np.pi - 1e-9), 0.0]):
+        R = npcalib.rodrigues(r)
+        th = float(np.linalg.norm(r))
+        assert abs(SC.rot_angle(R, np.eye(3)) - th) < 1e-12
+        assert SC.rot_angle(npcalib.rodrigues(SC.log_so3(R)), R) < 1e-14
+        if th > 0:   # the other representation is the same rotation
+            assert SC.rot_angle(npcalib.rodrigues(np.array(r) * (1 - 2 * np.pi / th)), R) < 1e-14
 
 
 # ---------------------------------------------------------------- mcc_stereo_calib_mask
@@ -118,6 +186,57 @@ def test_init_extrinsics_near_pi_and_identity():
         om, T = api.stereo_init_extrinsics(r1, t1, r2, t2)
         assert np.abs(npcalib.rodrigues(om) - R).max() < 1e-9, (om_true, om)
         assert np.abs(T - [-120.0, 0.0, 0.0]).max() < 1e-6
+
+
+@pytest.mark.parametrize("n", [4, 5, 16])
+@pytest.mark.parametrize("rig", SC.HALF_TURN)
+def test_init_extrinsics_at_a_half_turn(rig, n):
+    """Within noise of a half turn the views' logarithms land on both sides of pi, +(pi - e) a and -(pi - e) a:
+    the same rotation to 2e, opposite vectors.  Each view's relative rotation is the true R turned about R's own
+    axis by +2e-3 and -2e-3 rad alternately (n = 5: three against two) and by at most 1e-3 rad about each axis, so
+    it is within 2e-3 + sqrt(3) 1e-3 < 4e-3 rad of R, and a component-wise median of vectors in one representation
+    is within sqrt(3) 4e-3 < 7e-3 rad of it: the gate is 1e-2 rad.  T under the gate of the near-pi test above."""
+    om_true, T_true, _ = SC.rig_of(rig)
+    R_true = npcalib.rodrigues(om_true)
+    axis = om_true / np.linalg.norm(om_true)
+    rng = np.random.default_rng(40 + n)
+    r1 = np.column_stack([rng.uniform(-0.5, 0.5, n), rng.uniform(-0.5, 0.5, n), rng.uniform(-0.3, 0.3, n)])
+    t1 = np.column_stack([rng.uniform(-60, 60, n), rng.uniform(-40, 40, n), rng.uniform(500, 1200, n)])
+    r2, t2, logs = np.empty((n, 3)), np.empty((n, 3)), []
+    for v in range(n):
+        Rv = npcalib.rodrigues(rng.uniform(-1e-3, 1e-3, 3)) @ npcalib.rodrigues(axis * (2e-3 if v % 2 == 0 else -2e-3)) @ R_true
+        assert SC.rot_angle(Rv, R_true) < 4e-3
+        logs.append(SC.log_so3(Rv))
+        r2[v] = SC.log_so3(Rv @ npcalib.rodrigues(r1[v]))
+        t2[v] = Rv @ t1[v] + T_true
+    side = np.array(logs) @ axis
+    assert (side > 3.0).sum() == n // 2 and (side < -3.0).sum() == n - n // 2, side     # the inputs have both signs
+    om, T = api.stereo_init_extrinsics(r1, t1, r2, t2)
+    fig = dict(rig=rig, n=n, angle=SC.rot_angle(npcalib.rodrigues(om), R_true), dT=float(np.abs(T - T_true).max()),
+               om=om.tolist())
+    print("FIG", json.dumps(fig))
+    assert fig["angle"] <= 1e-2
+    assert fig["dT"] < 1e-6
+
+
+def test_init_extrinsics_is_unchanged_away_from_a_half_turn():
+    """Where no view's other representation is nearer to the reference view's vector, the start is the plain
+    component-wise median, bit for bit: on the rig of every existing test, with one view far off, and at a
+    quarter turn."""
+    for om_true in (SC.OM_TRUE, np.array([0.02, -0.03, np.pi / 2]), np.array([0.0, 2.4, 0.5])):
+        rng = np.random.default_rng(7)
+        R = npcalib.rodrigues(om_true)
+        r1 = rng.uniform(-0.4, 0.4, (9, 3))
+        t1 = rng.uniform(-50, 50, (9, 3)) + [0, 0, 800.0]
+        Rv = [npcalib.rodrigues(rng.normal(0, 0.02, 3)) @ R for _ in range(9)]
+        Rv[3] = npcalib.rodrigues([0.3, -0.2, 0.9]) @ R
+        r2 = np.array([SC.log_so3(Q @ npcalib.rodrigues(r)) for Q, r in zip(Rv, r1)])
+        t2 = np.array([Q @ t + SC.T_TRUE for Q, t in zip(Rv, t1)])
+        om, T = api.stereo_init_extrinsics(r1, t1, r2, t2)
+        # the library's own logarithm of each view, through one-view calls
+        one = [api.stereo_init_extrinsics(r1[v:v + 1], t1[v:v + 1], r2[v:v + 1], t2[v:v + 1]) for v in range(9)]
+        assert np.array_equal(om, np.median([o for o, _ in one], axis=0))
+        assert np.array_equal(T, np.median([t for _, t in one], axis=0))
 
 
 # ---------------------------------------------------------------- E and F

@@ -19,7 +19,8 @@ the cases and the assertions of the one-lane walk (tests/test_pinstereo_step_cpu
   * every view's squared error in each camera equals npstereocalib's at the returned parameters (1e-12 relative,
     or one spacing of a 1280 px coordinate on the view's rms where that is more).
 
-At least the first four accepted steps of each case are checked.
+At least the first four accepted steps of each case are checked.  The cases are step_cases() and, on rigs far from
+the identity, rig_step_cases().
 """
 import json
 
@@ -34,7 +35,7 @@ from test_pinstereo_step_cpu import check_trial
 
 pytestmark = pytest.mark.gpu
 
-CASES = {x[0]: x for x in SC.step_cases()}
+CASES = {x[0]: x for x in SC.step_cases() + SC.rig_step_cases()}
 RHO_CEILING = 1e-6
 
 # the largest rho over the checked steps, measured on an MI355X
@@ -43,6 +44,11 @@ MEASURED = {
     "17x65/aspect_same": 5.48e-11,
     "5x20/fix_intrinsic_nd4": 7.07e-15,
     "65x4/pp": 4.34e-11,
+    # stereo_calib_cases.rig_step_cases(): rigs on which A and B are far from what they are above
+    "5x20/toe_in": 1.13e-11,
+    "5x20/series_poses": 2.63e-11,
+    "9x20/roll90_same": 2.84e-12,
+    "5x20/forward_fix": 1.24e-12,
 }
 
 
