@@ -405,6 +405,91 @@ int mcc_stereo_calibrate(const mcc_stereo_calib_desc *d, double *K1, double *D1,
                          double *R, double *T, double *E, double *F, double *rvec, double *tvec,
                          double *view_rms, double *rms, int *iterations, int *status, double *device_ms);
 
+/* ---- pinhole rectification: cv::undistortPoints, cv::initUndistortRectifyMap + cv::remap, cv::undistort and
+ * cv::stereoRectify through cv::projectPoints' model, for the K, D, R, T that mcc_calibrate_camera and
+ * mcc_stereo_calibrate return.  DESIGN.md 7i states every rule; where it and OpenCV differ, it is the
+ * specification.
+ *
+ * D = k1 k2 p1 p2 [k3 [k4 k5 k6 [s1 s2 s3 s4]]] with nd in {0, 4, 5, 8, 12} as in mcc_pnp_desc; D == NULL or
+ * nd == 0 is zero distortion; the tilted sensor (nd = 14) is MCC_EINVAL.  K, R and P are row-major doubles:
+ * K and R 3 x 3, P with ld doubles per row (3, or 4 for the 3 x 4 P1 / P2 of mcc_stereo_rectify: only its
+ * first three columns are read).  R == NULL is the identity; P == NULL is the identity for points and K for
+ * maps.  Images are 8-bit with 1 or 3 interleaved channels and a row stride in bytes; bytes of a destination
+ * row past width * channels are never written.
+ *
+ * MCC_EINVAL with a message, before any device work, for a null required pointer, n < 0, a size that is not
+ * positive or is above 32767, channels other than 1 or 3, a stride shorter than a row, a bad nd, ld or map
+ * type, a zero focal length, a singular P R, or iterations outside 1..1000. */
+
+/* the map types of include/mcc_omnidir.h (MCC_OMNI_MAP_*) under model-neutral names; the encoding is the one
+ * documented there: MCC_MAP_FLOAT is two float[width * height] (u, v); MCC_MAP_FIXED is CV_16SC2 + CV_16UC1,
+ * with iu = cvRound(32 u), iv = cvRound(32 v): map1 = ((short)(iu >> 5), (short)(iv >> 5)) -- the cast wraps --
+ * and map2 = (iv & 31) * 32 + (iu & 31) */
+#define MCC_MAP_FLOAT 1
+#define MCC_MAP_FIXED 2
+
+#define MCC_CALIB_ZERO_DISPARITY 1024   /* cv::CALIB_ZERO_DISPARITY (mcc_stereo_rectify) */
+
+/* cv::undistortPoints: n pixels src[2n] -> dst[2n].  Per point x0 = (u - cx) / fx, y0 = (v - cy) / fy, then
+ * `iterations` rounds of the fixed-point inverse of the distortion (x, y) <- ((x0, y0) - tangential and prism
+ * terms at (x, y)) / radial factor at (x, y), then (X, Y, W) = R (x, y, 1), (x, y) = (X, Y) / W, then
+ * (P00 x + P01 y + P02, P10 x + P11 y + P12) / (P20 x + P21 y + P22).  mcc_solve_pnp_batch uses 20 rounds;
+ * OpenCV's 5 leave about 1e-2 px on a camera with k1 = -0.25.  n == 0 touches nothing.  device_ms (may be
+ * NULL): the kernel alone, by HIP events. */
+int mcc_undistort_points(int n, const double *src, const double *K, const double *D, int nd, const double *R,
+                         const double *P, int ld, int iterations, int device, double *dst, double *device_ms);
+
+/* cv::initUndistortRectifyMap for a width x height destination: pixel (j, i) reads the source at
+ * u = fx xd + cx, v = fy yd + cy, where (xd, yd) is the distortion of (X, Y) / W, (X, Y, W) = (P R)^-1 (j, i, 1)
+ * (the inverse on the host).  MCC_MAP_FLOAT writes two float[width * height], MCC_MAP_FIXED
+ * short[2 * width * height] and unsigned short[width * height].  device_ms as above. */
+int mcc_init_undistort_rectify_map(const double *K, const double *D, int nd, const double *R, const double *P,
+                                   int ld, int width, int height, int map_type, int device, void *map1,
+                                   void *map2, double *device_ms);
+
+/* cv::stereoRectify; host only, no device call.  Camera 2 sees a point X of camera 1's frame at R X + T
+ * (mcc_stereo_calibrate's R, T).  flags is 0 or MCC_CALIB_ZERO_DISPARITY; alpha < 0 keeps the focal length
+ * (no scaling), 0 <= alpha <= 1 scales between "only valid pixels" (0) and "every source pixel kept" (1);
+ * new_width == 0 takes the image size.  Out, each may be NULL: R1[9], R2[9] (camera frame -> rectified frame),
+ * P1[12], P2[12] (3 x 4), Q[16] (disparity to depth: Q (x, y, d, 1) ~ the point in camera 1's rectified frame,
+ * d = x1 - x2, or y1 - y2 for a vertical pair), roi1[4], roi2[4] (x, y, width, height of the all-valid
+ * region).  The baseline lies along x or along y of the rectified frame, whichever is nearer: P2[3] or P2[7]
+ * carries T f.  MCC_EINVAL also for T = 0, alpha > 1 and an unknown flag. */
+int mcc_stereo_rectify(const double *K1, const double *D1, const double *K2, const double *D2, int nd,
+                       int width, int height, const double *R, const double *T, int flags, double alpha,
+                       int new_width, int new_height, double *R1, double *R2, double *P1, double *P2,
+                       double *Q, int *roi1, int *roi2);
+
+/* cv::undistort / the remap of a rectified view in one call: the MCC_MAP_FIXED maps of (K, D, R, Knew) for
+ * new_w x new_h are built on the device, never leave it, and the image goes through cv::remap's INTER_LINEAR
+ * with BORDER_CONSTANT 0 (the kernel of mcc_omnidir_remap).  Knew == NULL is K; new_w == 0 takes the source
+ * size. */
+int mcc_undistort_image(const unsigned char *src, int src_w, int src_h, int channels, long long src_stride,
+                        const double *K, const double *D, int nd, const double *R, const double *Knew, int ld,
+                        int new_w, int new_h, int device, unsigned char *dst, long long dst_stride);
+
+/* The per-frame case: the fixed-point maps are built once at create and stay on the device with the source
+ * and destination images; every remap call is one upload, one kernel, one download. */
+typedef struct mcc_pinrect mcc_pinrect;
+
+typedef struct mcc_pinrect_desc {
+    const double *K;       /* [9]                                                 */
+    const double *D;       /* [nd] or NULL                                        */
+    int nd;
+    const double *R;       /* [9] or NULL                                         */
+    const double *P;       /* [3 * ld] or NULL (K)                                */
+    int ld;                /* doubles per row of P: 3 or 4                        */
+    int dst_width, dst_height;
+    int src_width, src_height;
+    int channels;          /* 1 or 3                                              */
+    int device;            /* HIP device ordinal                                  */
+} mcc_pinrect_desc;
+
+int mcc_pinrect_create(mcc_pinrect **out, const mcc_pinrect_desc *desc);
+void mcc_pinrect_destroy(mcc_pinrect *h);
+int mcc_pinrect_remap(mcc_pinrect *h, const unsigned char *src, long long src_stride, unsigned char *dst,
+                      long long dst_stride);
+
 #ifdef __cplusplus
 }
 #endif

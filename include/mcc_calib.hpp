@@ -15,7 +15,9 @@
  * with CALIB_RATIONAL_MODEL and 5 otherwise (a vector handed in with another size is resized; its leading entries
  * are the guess under CALIB_USE_INTRINSIC_GUESS).  Thin-prism and tilted-sensor flags throw.
  *
- * cv::stereoCalibrate for a pinhole pair is further down, over mcc_stereo_calibrate.
+ * cv::stereoCalibrate for a pinhole pair is further down, over mcc_stereo_calibrate, and after it
+ * the rectification of what the two return: undistortPoints, initUndistortRectifyMap, undistort, stereoRectify
+ * (DESIGN.md 7i).
  */
 #ifndef MCC_CALIB_HPP
 #define MCC_CALIB_HPP
@@ -106,6 +108,67 @@ double stereoCalibrate(const std::vector<std::vector<Vec3d>>& objectPoints,
                        TermCriteria criteria = TermCriteria(TermCriteria::COUNT + TermCriteria::EPS, 30, 1e-6),
                        std::vector<std::array<double, 2>>* perViewErrors = nullptr, StereoCalibInfo* info = nullptr,
                        int device = 0);
+
+/*
+ * Rectification over mcc_undistort_points, mcc_init_undistort_rectify_map, mcc_undistort_image and
+ * mcc_stereo_rectify, with cv::'s names and argument order:
+ *
+ *   void undistortPoints(InputArray src, OutputArray dst, InputArray cameraMatrix, InputArray distCoeffs,
+ *                        InputArray R = noArray(), InputArray P = noArray());
+ *   void initUndistortRectifyMap(InputArray cameraMatrix, InputArray distCoeffs, InputArray R, InputArray newCameraMatrix,
+ *                                Size size, int m1type, OutputArray map1, OutputArray map2);
+ *   void undistort(InputArray src, OutputArray dst, InputArray cameraMatrix, InputArray distCoeffs,
+ *                  InputArray newCameraMatrix = noArray());
+ *   void stereoRectify(InputArray cameraMatrix1, InputArray distCoeffs1, InputArray cameraMatrix2, InputArray distCoeffs2,
+ *                      Size imageSize, InputArray R, InputArray T, OutputArray R1, OutputArray R2, OutputArray P1,
+ *                      OutputArray P2, OutputArray Q, int flags = CALIB_ZERO_DISPARITY, double alpha = -1,
+ *                      Size newImageSize = Size(), Rect* validPixROI1 = 0, Rect* validPixROI2 = 0);
+ *
+ * distCoeffs holds 0, 4, 5, 8 or 12 values; R is 3 x 3 (9 values) or empty (identity); P / newCameraMatrix is 3 x 3
+ * (9 values), 3 x 4 (12 values, its first three columns are read) or empty (the identity for points, cameraMatrix for
+ * maps).  Wrong sizes throw std::invalid_argument; whatever the C ABI refuses or the device fails at throws
+ * std::runtime_error with the library's message.  Where 7i and OpenCV differ (20 rounds of the distortion's inverse
+ * where OpenCV runs 5), 7i holds.
+ */
+enum { CALIB_ZERO_DISPARITY = MCC_CALIB_ZERO_DISPARITY };
+enum { MAP_32FC1 = MCC_MAP_FLOAT, MAP_16SC2 = MCC_MAP_FIXED };   // m1type
+
+struct Rect {
+    int x = 0, y = 0, width = 0, height = 0;
+};
+
+// an 8-bit image of 1 or 3 interleaved channels; step is the row stride in bytes (0: packed rows)
+struct Image {
+    unsigned char* data = nullptr;
+    int width = 0, height = 0, channels = 1;
+    long long step = 0;
+    long long stride() const { return step ? step : (long long)width * channels; }
+};
+
+void undistortPoints(const std::vector<Vec2d>& src, std::vector<Vec2d>& dst, const std::array<double, 9>& cameraMatrix,
+                     const std::vector<double>& distCoeffs, const std::vector<double>& R = {},
+                     const std::vector<double>& P = {}, int iterations = 20, int device = 0);
+
+// m1type MAP_16SC2: map1 holds short[2 w h], map2 unsigned short[w h]; MAP_32FC1: both hold float[w h].
+// The maps are returned as raw bytes of those types.
+void initUndistortRectifyMap(const std::array<double, 9>& cameraMatrix, const std::vector<double>& distCoeffs,
+                             const std::vector<double>& R, const std::vector<double>& newCameraMatrix, Size size,
+                             int m1type, std::vector<unsigned char>& map1, std::vector<unsigned char>& map2,
+                             int device = 0);
+
+// dst must point at newSize (or, with an empty newSize, src's size) pixels of src's channel count.  With R and
+// newCameraMatrix = P1 / P2 this is the remap of one rectified view.
+void undistort(const Image& src, const Image& dst, const std::array<double, 9>& cameraMatrix,
+               const std::vector<double>& distCoeffs, const std::vector<double>& newCameraMatrix = {},
+               Size newSize = Size(), const std::vector<double>& R = {}, int device = 0);
+
+// host only
+void stereoRectify(const std::array<double, 9>& cameraMatrix1, const std::vector<double>& distCoeffs1,
+                   const std::array<double, 9>& cameraMatrix2, const std::vector<double>& distCoeffs2, Size imageSize,
+                   const std::array<double, 9>& R, const Vec3d& T, std::array<double, 9>& R1, std::array<double, 9>& R2,
+                   std::array<double, 12>& P1, std::array<double, 12>& P2, std::array<double, 16>& Q,
+                   int flags = CALIB_ZERO_DISPARITY, double alpha = -1, Size newImageSize = Size(),
+                   Rect* validPixROI1 = nullptr, Rect* validPixROI2 = nullptr);
 
 }  // namespace calib
 }  // namespace mcc

@@ -97,6 +97,7 @@ CV_CALIB_FIX_K4, CV_CALIB_FIX_K5, CV_CALIB_FIX_K6, CV_CALIB_RATIONAL_MODEL = 204
 CALIB_CONVERGED, CALIB_COUNT, CALIB_STALLED = 0, 1, 2
 # cv::stereoCalibrate's own (mcc_stereo_calibrate)
 CV_CALIB_FIX_INTRINSIC, CV_CALIB_SAME_FOCAL_LENGTH, CV_CALIB_USE_EXTRINSIC_GUESS = 256, 512, 1 << 22
+CV_CALIB_ZERO_DISPARITY = 1024   # cv::stereoRectify's (mcc_stereo_rectify)
 
 
 class _StereoCalibDesc(ctypes.Structure):
@@ -104,6 +105,12 @@ class _StereoCalibDesc(ctypes.Structure):
                 ("image_width", ctypes.c_int), ("image_height", ctypes.c_int), ("flags", ctypes.c_int),
                 ("nd", ctypes.c_int), ("crit_type", ctypes.c_int), ("max_count", ctypes.c_int), ("eps", ctypes.c_double),
                 ("device", ctypes.c_int), ("trials", _i32p)]
+
+
+class _PinRectDesc(ctypes.Structure):
+    _fields_ = [("K", _f64p), ("D", _f64p), ("nd", ctypes.c_int), ("R", _f64p), ("P", _f64p), ("ld", ctypes.c_int),
+                ("dst_width", ctypes.c_int), ("dst_height", ctypes.c_int), ("src_width", ctypes.c_int),
+                ("src_height", ctypes.c_int), ("channels", ctypes.c_int), ("device", ctypes.c_int)]
 
 
 _LIB = None
@@ -250,10 +257,22 @@ def lib():
                 ("mcc_stereo_calib_mask", [ctypes.c_int, ctypes.c_int, _i32p, _i32p]),
                 ("mcc_stereo_init_extrinsics", [ctypes.c_int] + [_f64p] * 6),
                 ("mcc_stereo_epipolar", [_f64p] * 6),
-                ("mcc_stereo_calibrate", [ctypes.POINTER(_StereoCalibDesc)] + [_f64p] * 12 + [_i32p, _i32p, _f64p])):
+                ("mcc_stereo_calibrate", [ctypes.POINTER(_StereoCalibDesc)] + [_f64p] * 12 + [_i32p, _i32p, _f64p]),
+                ("mcc_undistort_points", [ctypes.c_int, _f64p, _f64p, _f64p, ctypes.c_int, _f64p, _f64p] +
+                 [ctypes.c_int] * 3 + [_f64p, _f64p]),
+                ("mcc_init_undistort_rectify_map", [_f64p, _f64p, ctypes.c_int, _f64p, _f64p] + [ctypes.c_int] * 5 +
+                 [ctypes.c_void_p] * 2 + [_f64p]),
+                ("mcc_stereo_rectify", [_f64p] * 4 + [ctypes.c_int] * 3 + [_f64p, _f64p, ctypes.c_int, ctypes.c_double,
+                                                                          ctypes.c_int, ctypes.c_int] + [_f64p] * 5 +
+                 [_i32p, _i32p]),
+                ("mcc_undistort_image", [_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ll, _f64p, _f64p, ctypes.c_int,
+                                         _f64p, _f64p] + [ctypes.c_int] * 4 + [_u8p, _ll]),
+                ("mcc_pinrect_create", [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_PinRectDesc)]),
+                ("mcc_pinrect_destroy", [ctypes.c_void_p]),
+                ("mcc_pinrect_remap", [ctypes.c_void_p, _u8p, _ll, _u8p, _ll])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
-        for name in ("mcc_omnirect_destroy", "mcc_omnirecon_destroy"):
+        for name in ("mcc_omnirect_destroy", "mcc_omnirecon_destroy", "mcc_pinrect_destroy"):
             if hasattr(L, name):
                 getattr(L, name).restype = None
         _LIB = L
@@ -1119,6 +1138,134 @@ class OmniRectifier:
         ms = ctypes.c_double(0)
         _check(lib().mcc_omnirect_time_remap(self.h, int(n_frames), ctypes.byref(ms)), "mcc_omnirect_time_remap")
         return ms.value
+
+
+# ---------------------------------------------------------------- pinhole rectification
+# include/mcc.h: cv::undistortPoints, cv::initUndistortRectifyMap, cv::undistort, cv::stereoRectify for the K, D, R, T
+# of calibrate_camera and stereo_calibrate.
+def _dist(D):
+    """(D as float64 or None, nd)"""
+    if D is None:
+        return None, 0
+    D = np.ascontiguousarray(D, np.float64).reshape(-1)
+    return (D, D.size) if D.size else (None, 0)
+
+
+def _proj(P, what):
+    """(P as a contiguous 3 x 3 or 3 x 4 array or None, its doubles per row)"""
+    if P is None:
+        return None, 3
+    P = np.ascontiguousarray(P, np.float64)
+    if P.shape not in ((3, 3), (3, 4)):
+        raise MccError(f"{what} must be 3 x 3 or 3 x 4")
+    return P, P.shape[1]
+
+
+def undistort_points(src, K, D=None, R=None, P=None, iterations=20, device=0, return_ms=False):
+    """cv::undistortPoints (mcc_undistort_points): pixels [n, 2] -> ideal points [n, 2], after R (a 3 x 3 matrix or a
+    rotation vector) and through P (3 x 3 or 3 x 4) when given.  D holds 0, 4, 5, 8 or 12 coefficients.  The inverse
+    of the distortion runs `iterations` fixed-point rounds (20, as solve_pnp's; OpenCV runs 5)."""
+    pts = np.ascontiguousarray(src, np.float64).reshape(-1, 2)
+    K, R = _mat3(K, "K"), _mat3(R, "R", True)
+    (D, nd), (P, ld) = _dist(D), _proj(P, "P")
+    out, ms = np.zeros_like(pts), np.zeros(1)
+    _check(lib().mcc_undistort_points(pts.shape[0], _ptr(pts, _f64p), _ptr(K, _f64p), _ptr(D, _f64p), nd, _ptr(R, _f64p),
+                                      _ptr(P, _f64p), ld, int(iterations), device, _ptr(out, _f64p), _ptr(ms, _f64p)),
+           "mcc_undistort_points")
+    return (out, float(ms[0])) if return_ms else out
+
+
+def init_undistort_rectify_map(K, D, R, P, size, map_type=MAP_FIXED, device=0, return_ms=False):
+    """cv::initUndistortRectifyMap for size = (width, height) (mcc_init_undistort_rectify_map): MAP_FLOAT gives two
+    float32 [h, w] maps (u, v), MAP_FIXED int16 [h, w, 2] and uint16 [h, w] (CV_16SC2 + CV_16UC1).  R None is the
+    identity, P None is K."""
+    K, R = _mat3(K, "K"), _mat3(R, "R", True)
+    (D, nd), (P, ld) = _dist(D), _proj(P, "P")
+    w, h = int(size[0]), int(size[1])
+    shape = (max(h, 0), max(w, 0))
+    if map_type == MAP_FLOAT:
+        m1, m2 = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+    else:
+        m1, m2 = np.zeros(shape + (2,), np.int16), np.zeros(shape, np.uint16)
+    ms = np.zeros(1)
+    _check(lib().mcc_init_undistort_rectify_map(_ptr(K, _f64p), _ptr(D, _f64p), nd, _ptr(R, _f64p), _ptr(P, _f64p), ld, w, h,
+                                                map_type, device, m1.ctypes.data_as(ctypes.c_void_p),
+                                                m2.ctypes.data_as(ctypes.c_void_p), _ptr(ms, _f64p)),
+           "mcc_init_undistort_rectify_map")
+    return (m1, m2, float(ms[0])) if return_ms else (m1, m2)
+
+
+def stereo_rectify(K1, D1, K2, D2, image_size, R, T, flags=CV_CALIB_ZERO_DISPARITY, alpha=-1.0, new_size=None):
+    """cv::stereoRectify (mcc_stereo_rectify; host code, no GPU): (R1, R2, P1 [3, 4], P2 [3, 4], Q [4, 4], roi1, roi2)
+    of the pair whose second camera sees X at R X + T; a roi is (x, y, width, height).  D1 and D2 hold the same number
+    of coefficients.  flags is 0 or CV_CALIB_ZERO_DISPARITY, alpha negative (keep the focal length) or in 0..1,
+    new_size = (width, height) or None for image_size."""
+    K1, K2, R, T = _mat3(K1, "K1"), _mat3(K2, "K2"), _mat3(R, "R", True), _vec(T, 3, "T")
+    (D1, nd), (D2, nd2) = _dist(D1), _dist(D2)
+    if D1 is not None and D2 is not None and nd != nd2:
+        raise MccError("stereo_rectify: D1 and D2 must hold the same number of coefficients")
+    nw, nh = (0, 0) if new_size is None else (int(new_size[0]), int(new_size[1]))
+    R1, R2, P1, P2, Q = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros((3, 4)), np.zeros((3, 4)), np.zeros((4, 4))
+    roi1, roi2 = np.zeros(4, np.int32), np.zeros(4, np.int32)
+    _check(lib().mcc_stereo_rectify(_ptr(K1, _f64p), _ptr(D1, _f64p), _ptr(K2, _f64p), _ptr(D2, _f64p), max(nd, nd2),
+                                    int(image_size[0]), int(image_size[1]), _ptr(R, _f64p), _ptr(T, _f64p), int(flags),
+                                    float(alpha), nw, nh, *[_ptr(a, _f64p) for a in (R1, R2, P1, P2, Q)],
+                                    _ptr(roi1, _i32p), _ptr(roi2, _i32p)), "mcc_stereo_rectify")
+    return R1, R2, P1, P2, Q, tuple(int(v) for v in roi1), tuple(int(v) for v in roi2)
+
+
+def undistort_image(src, K, D=None, Knew=None, new_size=None, R=None, dst=None, device=0):
+    """cv::undistort, or with R and Knew = P1 / P2 the remap of one rectified view (mcc_undistort_image): the
+    fixed-point maps and the remap in one call; new_size = (width, height), None for the source size."""
+    src, sw, sh, c, sstride = _image(src, "src")
+    K, R = _mat3(K, "K"), _mat3(R, "R", True)
+    (D, nd), (Knew, ld) = _dist(D), _proj(Knew, "Knew")
+    w, h = (sw, sh) if new_size is None else (int(new_size[0]), int(new_size[1]))
+    dst, dstride = _dst_image(dst, w, h, c, src.ndim == 2)
+    _check(lib().mcc_undistort_image(_ptr(src, _u8p), sw, sh, c, sstride, _ptr(K, _f64p), _ptr(D, _f64p), nd, _ptr(R, _f64p),
+                                     _ptr(Knew, _f64p), ld, w, h, device, _ptr(dst, _u8p), dstride), "mcc_undistort_image")
+    return dst
+
+
+class PinholeRectifier:
+    """The per-frame case of undistort_image (mcc_pinrect): the fixed-point maps of (K, D, R, P) for dst_size are built
+    once and stay on the device with the two images."""
+
+    def __init__(self, K, D, src_size, channels=1, R=None, P=None, dst_size=None, device=0):
+        (D, nd), (P, ld) = _dist(D), _proj(P, "P")
+        self._keep = [_mat3(K, "K"), D, _mat3(R, "R", True), P]
+        self.src_size = (int(src_size[0]), int(src_size[1]))
+        self.dst_size = self.src_size if dst_size is None else (int(dst_size[0]), int(dst_size[1]))
+        self.channels = int(channels)
+        d = _PinRectDesc()
+        d.K, d.D, d.R, d.P = (_ptr(a, _f64p) for a in self._keep)
+        d.nd, d.ld, d.device = nd, ld, device
+        d.dst_width, d.dst_height = self.dst_size
+        d.src_width, d.src_height = self.src_size
+        d.channels = self.channels
+        h = ctypes.c_void_p()
+        _check(lib().mcc_pinrect_create(ctypes.byref(h), ctypes.byref(d)), "mcc_pinrect_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcc_pinrect_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def remap(self, src, dst=None):
+        """One frame (uint8 [h, w] or [h, w, channels] of src_size) through the resident maps."""
+        src, sw, sh, c, sstride = _image(src, "src")
+        if (sw, sh) != self.src_size or c != self.channels:
+            raise MccError(f"src must be {self.src_size[1]} x {self.src_size[0]} x {self.channels}")
+        dst, dstride = _dst_image(dst, self.dst_size[0], self.dst_size[1], c, src.ndim == 2)
+        _check(lib().mcc_pinrect_remap(self.h, _ptr(src, _u8p), sstride, _ptr(dst, _u8p), dstride), "mcc_pinrect_remap")
+        return dst
 
 
 def omnidir_sgbm(left, right, num_disparities, sad_window_size, device=0):

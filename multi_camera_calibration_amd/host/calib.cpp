@@ -1,8 +1,11 @@
 // calib.cpp -- mcc::calib::calibrateCamera and initCameraMatrix2D (include/mcc_calib.hpp): cv::calibrateCamera's
 // argument order over mcc_calibrate_camera / mcc_init_camera_matrix (reference call sites
-// src/multicalib.cpp:254-256, samples/random_pattern_calibration.cpp:159, src/ccalib.cpp:423).
+// src/multicalib.cpp:254-256, samples/random_pattern_calibration.cpp:159, src/ccalib.cpp:423), stereoCalibrate over
+// mcc_stereo_calibrate, and the rectification calls undistortPoints, initUndistortRectifyMap, undistort and stereoRectify
+// over mcc_undistort_points, mcc_init_undistort_rectify_map, mcc_undistort_image and mcc_stereo_rectify.
 #include "mcc_calib.hpp"
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 
@@ -151,6 +154,94 @@ double stereoCalibrate(const std::vector<std::vector<Vec3d>>& objectPoints,
             }
     }
     return rms;
+}
+
+// ---------------------------------------------------------------- rectification
+namespace {
+
+const double* rotation(const std::vector<double>& R, const char* who) {
+    if (R.empty()) return nullptr;
+    if (R.size() != 9) throw std::invalid_argument(std::string(who) + ": R must hold 9 values (3 x 3) or none");
+    return R.data();
+}
+
+// P / newCameraMatrix and its doubles per row
+const double* projection(const std::vector<double>& P, int& ld, const char* who) {
+    ld = P.size() == 12 ? 4 : 3;
+    if (P.empty()) return nullptr;
+    if (P.size() != 9 && P.size() != 12) throw std::invalid_argument(std::string(who) + ": P must hold 9 values (3 x 3), 12 (3 x 4) or none");
+    return P.data();
+}
+
+}  // namespace
+
+void undistortPoints(const std::vector<Vec2d>& src, std::vector<Vec2d>& dst, const std::array<double, 9>& cameraMatrix,
+                     const std::vector<double>& distCoeffs, const std::vector<double>& R, const std::vector<double>& P,
+                     int iterations, int device) {
+    const char* who = "undistortPoints";
+    int ld = 3;
+    const double* Rp = rotation(R, who);
+    const double* Pp = projection(P, ld, who);
+    dst.assign(src.size(), Vec2d{});
+    const int rc = mcc_undistort_points((int)src.size(), src.empty() ? nullptr : src[0].data(), cameraMatrix.data(),
+                                        distCoeffs.empty() ? nullptr : distCoeffs.data(), (int)distCoeffs.size(), Rp, Pp, ld,
+                                        iterations, device, dst.empty() ? nullptr : dst[0].data(), nullptr);
+    if (rc != MCC_OK) throw std::runtime_error(std::string(who) + ": " + mcc_last_error());
+}
+
+void initUndistortRectifyMap(const std::array<double, 9>& cameraMatrix, const std::vector<double>& distCoeffs,
+                             const std::vector<double>& R, const std::vector<double>& newCameraMatrix, Size size, int m1type,
+                             std::vector<unsigned char>& map1, std::vector<unsigned char>& map2, int device) {
+    const char* who = "initUndistortRectifyMap";
+    int ld = 3;
+    const double* Rp = rotation(R, who);
+    const double* Pp = projection(newCameraMatrix, ld, who);
+    if (m1type <= 0) m1type = MAP_16SC2;   // as cv::initUndistortRectifyMap
+    const size_t px = size.width > 0 && size.height > 0 ? (size_t)size.width * size.height : 0;
+    map1.assign(std::max<size_t>(px * 4, 1), 0);
+    map2.assign(std::max<size_t>(px * (m1type == MAP_32FC1 ? 4 : 2), 1), 0);
+    const int rc = mcc_init_undistort_rectify_map(cameraMatrix.data(), distCoeffs.empty() ? nullptr : distCoeffs.data(),
+                                                  (int)distCoeffs.size(), Rp, Pp, ld, size.width, size.height, m1type, device,
+                                                  map1.data(), map2.data(), nullptr);
+    if (rc != MCC_OK) throw std::runtime_error(std::string(who) + ": " + mcc_last_error());
+}
+
+void undistort(const Image& src, const Image& dst, const std::array<double, 9>& cameraMatrix,
+               const std::vector<double>& distCoeffs, const std::vector<double>& newCameraMatrix, Size newSize,
+               const std::vector<double>& R, int device) {
+    const char* who = "undistort";
+    int ld = 3;
+    const double* Rp = rotation(R, who);
+    const double* Pp = projection(newCameraMatrix, ld, who);
+    const bool keep = newSize.width <= 0 || newSize.height <= 0;   // Size::empty()
+    const int w = keep ? src.width : newSize.width, h = keep ? src.height : newSize.height;
+    if (dst.width != w || dst.height != h || dst.channels != src.channels)
+        throw std::invalid_argument(std::string(who) + ": dst must be the new size (or src's) with src's channels");
+    const int rc = mcc_undistort_image(src.data, src.width, src.height, src.channels, src.stride(), cameraMatrix.data(),
+                                       distCoeffs.empty() ? nullptr : distCoeffs.data(), (int)distCoeffs.size(), Rp, Pp, ld, w,
+                                       h, device, dst.data, dst.stride());
+    if (rc != MCC_OK) throw std::runtime_error(std::string(who) + ": " + mcc_last_error());
+}
+
+void stereoRectify(const std::array<double, 9>& cameraMatrix1, const std::vector<double>& distCoeffs1,
+                   const std::array<double, 9>& cameraMatrix2, const std::vector<double>& distCoeffs2, Size imageSize,
+                   const std::array<double, 9>& R, const Vec3d& T, std::array<double, 9>& R1, std::array<double, 9>& R2,
+                   std::array<double, 12>& P1, std::array<double, 12>& P2, std::array<double, 16>& Q, int flags, double alpha,
+                   Size newImageSize, Rect* validPixROI1, Rect* validPixROI2) {
+    // one nd for both cameras: the shorter vector is padded with zeros
+    const size_t nd = std::max(distCoeffs1.size(), distCoeffs2.size());
+    std::vector<double> d1(distCoeffs1), d2(distCoeffs2);
+    d1.resize(nd, 0.0);
+    d2.resize(nd, 0.0);
+    int roi[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    const int rc = mcc_stereo_rectify(cameraMatrix1.data(), nd ? d1.data() : nullptr, cameraMatrix2.data(),
+                                      nd ? d2.data() : nullptr, (int)nd, imageSize.width, imageSize.height, R.data(), T.data(),
+                                      flags, alpha, newImageSize.width, newImageSize.height, R1.data(), R2.data(), P1.data(),
+                                      P2.data(), Q.data(), roi[0], roi[1]);
+    if (rc != MCC_OK) throw std::runtime_error(std::string("stereoRectify: ") + mcc_last_error());
+    Rect* out[2] = {validPixROI1, validPixROI2};
+    for (int k = 0; k < 2; ++k)
+        if (out[k]) *out[k] = Rect{roi[k][0], roi[k][1], roi[k][2], roi[k][3]};
 }
 
 }  // namespace calib
