@@ -1,7 +1,8 @@
 // mcc_omnicalib_host.hpp -- host helpers shared by mcc_omnicalib_api.cpp and mcc_omnistereo_api.cpp:
 // the error path of the C ABI, an owning device buffer, and the handles' common base with the one
 // implementation of everything that drives the device loop (state, graphs, step launches and the
-// bodies of jacobian / optimize / rms / time_steps).
+// bodies of jacobian / optimize / rms / time_steps).  The pinhole host files include it for the error
+// path, DBuf, OcEvents, mul3 and rodrigues_host.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,6 +40,32 @@ struct DBuf {
         return e;
     }
 };
+
+// the two events around a timed stretch of device work
+struct OcEvents {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~OcEvents() {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create() {
+        hipError_t e = hipEventCreate(&ev[0]);
+        return e == hipSuccess ? hipEventCreate(&ev[1]) : e;
+    }
+    hipError_t elapsed(double* ms) {
+        hipError_t e = hipEventSynchronize(ev[1]);
+        float f = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&f, ev[0], ev[1]);
+        *ms = f;
+        return e;
+    }
+};
+
+// C = A B, row-major 3 x 3
+void mul3(const double* A, const double* B, double* C) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
+}
 
 // de-interleaves C w-tuples (pattern points: 3, image points: 2) into w device arrays
 hipError_t oc_upload_soa(const double* src, int w, size_t C, std::initializer_list<DBuf<double>*> dst) {

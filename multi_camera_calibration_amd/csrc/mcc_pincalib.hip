@@ -6,13 +6,14 @@
 //              mcc_pincalib_device.hpp; after a rejected trial the stored sums are reused), damps and
 //              eliminates its 6 x 6 pose block, keeps Y_v, z_v for the back-substitution and writes its
 //              contribution to the reduced 12 x 12 system.  The contributions are summed in view order
-//              by a two-level last-arriver ticket (groups of ~sqrt(n) views, then the groups, as the
-//              omnidir loop's OcLayout / gsum); the last arriver solves the reduced system for the
-//              global step dc.
+//              by a two-level last-arriver ticket (pin_reduce, mcc_pinloop_device.hpp); the last arriver
+//              solves the reduced system for the global step dc.
 //   k_pc_try   back-substitutes the view's pose step, evaluates the squared error of the trial
-//              parameters and sums it over the views the same way; the last arriver accepts the trial
-//              (en <= err: parameters, error and lambda / 10) or rejects it (lambda x 10) and runs the
-//              stop tests.  With st->init it only evaluates the starting point.
+//              parameters and sums it over the views the same way (pin_sum_err); the last arriver
+//              accepts or rejects the trial and runs the stop tests (pin_verdict; the policy is pc_next,
+//              mcc_pincalib_internal.h).  With st->init it only evaluates the starting point.
+// The sums and the verdict are shared with mcc_pinstereo.hip; what is this kernel's own in the verdict is
+// how the 12 global slots, still live in g and gt, enter the step's norms and are committed.
 // No workgroup waits for another: a hand-off is a ticket or the kernel boundary.  The loop state lives
 // in PcState; a launch after `done` returns at once, so the host enqueues trials in batches.
 // Hand-offs inside a launch are 8-byte sc1 stores and loads around oc_arrive (mcc_omnicalib_device.hpp).
@@ -21,6 +22,7 @@
 #include "mcc_omnicalib_device.hpp"
 #include "mcc_pincalib_device.hpp"
 #include "mcc_pincalib_internal.h"
+#include "mcc_pinloop_device.hpp"
 
 namespace mcc {
 
@@ -51,13 +53,7 @@ __global__ __launch_bounds__(64) void k_pc_lin(PcArgs a) {
     for (int i = lane; i < kPcYz; i += 64) a.Yz[(size_t)v * kPcYz + i] = Yz[i];
     for (int e = lane; e < PcCtr::N; e += 64) oc_st(a.contrib + (size_t)v * PcCtr::N + e, ctr[e]);
 
-    const int grp = v / a.group_size, g0 = grp * a.group_size, gn = min(a.group_size, a.n - g0);
-    if (!oc_arrive(&a.cnt[grp], gn)) return;
-    for (int e = lane; e < PcCtr::N; e += 64)
-        oc_st(a.gsum + (size_t)grp * PcCtr::N + e, oc_sum<PcCtr::N>(a.contrib + (size_t)g0 * PcCtr::N + e, gn));
-    if (!oc_arrive(&a.cnt[a.n_groups], a.n_groups)) return;
-    for (int e = lane; e < PcCtr::N; e += 64) tot[e] = oc_sum<PcCtr::N>(a.gsum + e, a.n_groups);
-    __syncthreads();
+    if (!pin_reduce<PcCtr::N>(a, v, lane, tot)) return;
     double dc[kPcG];
     const bool ok = pc_reduced_solve(tot, lambda, a.mask, dc);
     if (lane == 0) {
@@ -93,70 +89,17 @@ __global__ __launch_bounds__(64) void k_pc_try(PcArgs a) {
         }
         oc_st(a.esq_t + v, sq);
     }
-    int* cnt = a.cnt + a.n_groups + 1;
-    const int grp = v / a.group_size, g0 = grp * a.group_size, gn = min(a.group_size, a.n - g0);
-    if (!oc_arrive(&cnt[grp], gn)) return;
-    {
-        const double gs = oc_sum<1>(a.esq_t + g0, gn);
-        if (lane == 0) oc_st(a.egs + grp, gs);
-    }
-    if (!oc_arrive(&cnt[a.n_groups], a.n_groups)) return;
-    const double en = oc_sum<1>(a.egs, a.n_groups);
-
-    // ---- the last arriver: accept or reject, stop tests
-    const int iter = st->iter, tries = st->tries, trials = st->trials, fail = st->fail;
-    const int crit = st->crit_type, max_count = st->max_count;
-    const double eps = st->eps, lambda = st->lambda, err = st->err;
-    if (init) {
-        for (int i = lane; i < a.n; i += 64) a.esq[i] = oc_ld(a.esq_t + i);
-        if (lane == 0) {
-            st->err = en;
-            st->init = 0;
-            st->relin = 1;
-            if (!(fabs(en) < 1.7e308)) { st->done = 1; st->status = kPcNotFinite; }
-        }
-        return;
-    }
-    const bool accept = !fail && en <= err;   // (a NaN error is a rejection)
-    if (!accept) {
-        if (lane == 0) {
-            st->trials = trials + 1;
-            st->lambda = lambda * 10.0;
-            st->tries = tries + 1;
-            st->relin = 0;
-            if (tries + 1 >= 10) { st->done = 1; st->status = kPcStalled; }
-        }
-        return;
-    }
-    double dn = 0.0, xn = 0.0;
-    for (int i = lane; i < 6 * a.n; i += 64) {
-        const double xo = a.x[i], xw = oc_ld(a.xt + i), d = xw - xo;
-        dn += d * d;
-        xn += xo * xo;
-        a.x[i] = xw;
-    }
-    dn = pnp_wave_sum(dn);
-    xn = pnp_wave_sum(xn);
+    double en;
+    if (!pin_sum_err<1>(a, v, lane, en)) return;
+    pin_verdict<1>(a, lane, init, en, [&](double& dn, double& xn) {
 #pragma unroll
-    for (int k = 0; k < kPcG; ++k) {
-        const double d = gt[k] - g[k];
-        dn += d * d;
-        xn += g[k] * g[k];
-        if (lane == 0) a.glob[k] = gt[k];
-    }
-    for (int i = lane; i < a.n; i += 64) a.esq[i] = oc_ld(a.esq_t + i);
-    const double change = sqrt(dn) / sqrt(xn);
-    if (lane == 0) {
-        st->trials = trials + 1;
-        st->iter = iter + 1;
-        st->tries = 0;
-        st->relin = 1;
-        st->err = en;
-        st->change = change;
-        st->lambda = fmax(lambda * 0.1, 1e-12);
-        if ((crit & 2) && change < eps) { st->done = 1; st->status = kPcConverged; }
-        else if ((crit & 1) && iter + 1 >= max_count) { st->done = 1; st->status = kPcCount; }
-    }
+        for (int k = 0; k < kPcG; ++k) {
+            const double d = gt[k] - g[k];
+            dn += d * d;
+            xn += g[k] * g[k];
+            if (lane == 0) a.glob[k] = gt[k];
+        }
+    });
 }
 
 }  // namespace mcc

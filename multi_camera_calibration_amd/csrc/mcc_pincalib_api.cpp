@@ -1,8 +1,8 @@
 // mcc_pincalib_api.cpp -- host side of mcc_calibrate_camera, mcc_init_camera_matrix and mcc_calib_mask
 // (include/mcc.h).  The host checks the descriptor before any device call, finds the start (the closed
-// form of cv::initCameraMatrix2D, or the caller's guess), seeds the poses with one mcc_solve_pnp_batch
-// and then only launches trials (k_pc_lin + k_pc_try, mcc_pincalib.hip) in batches, reading the
-// device-resident loop state between batches.
+// form of cv::initCameraMatrix2D, or the caller's guess), seeds the poses (pin_seed_poses) and hands the
+// loop to PinLoop (mcc_pinloop_host.hpp) with its two launches, k_pc_lin and k_pc_try (mcc_pincalib.hip);
+// what is left here is the start, the unpacking of the slots and the rms.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -11,21 +11,13 @@
 #include <vector>
 
 #include "../../include/mcc.h"
-#include "mcc_omnicalib_host.hpp"
-#include "mcc_pincalib_internal.h"
+#include "mcc_pinloop_host.hpp"
 
 namespace {
 
-constexpr int kKnownFlags = MCC_CALIB_USE_INTRINSIC_GUESS | MCC_CALIB_FIX_ASPECT_RATIO | MCC_CALIB_FIX_PRINCIPAL_POINT |
-                            MCC_CALIB_ZERO_TANGENT_DIST | MCC_CALIB_FIX_FOCAL_LENGTH | MCC_CALIB_FIX_K1 |
-                            MCC_CALIB_FIX_K2 | MCC_CALIB_FIX_K3 | MCC_CALIB_FIX_K4 | MCC_CALIB_FIX_K5 |
-                            MCC_CALIB_FIX_K6 | MCC_CALIB_RATIONAL_MODEL;
-constexpr int kTrialBatch = 8;       // trials enqueued between two reads of the state
-constexpr int kEpsOnlyCount = 1000;  // accepted steps at most when the criteria have no count
-
 int pc_mask(const char* who, int flags, int nd, int* m) {
-    if (flags & ~kKnownFlags)
-        return oc_fail(MCC_EINVAL, std::string(who) + ": unsupported flag bits " + std::to_string(flags & ~kKnownFlags) +
+    if (flags & ~kPinCameraFlags)
+        return oc_fail(MCC_EINVAL, std::string(who) + ": unsupported flag bits " + std::to_string(flags & ~kPinCameraFlags) +
                                        " (thin prism, tilted sensor and the solver choices are not restated)");
     if (nd != 4 && nd != 5 && nd != 8) return oc_fail(MCC_EINVAL, std::string(who) + ": nd must be 4, 5 or 8");
     const bool focal = !(flags & MCC_CALIB_FIX_FOCAL_LENGTH), pp = !(flags & MCC_CALIB_FIX_PRINCIPAL_POINT);
@@ -48,17 +40,8 @@ int pc_mask(const char* who, int flags, int nd, int* m) {
 int pc_check_views(const char* who, const mcc_calib_desc* d, bool* planar) {
     const std::string w(who);
     if (!d) return oc_fail(MCC_EINVAL, w + ": null descriptor");
-    if (d->n_views <= 0) return oc_fail(MCC_EINVAL, w + ": n_views must be positive");
-    if (!d->view_off || !d->obj || !d->img) return oc_fail(MCC_EINVAL, w + ": null pointer in the descriptor");
-    if (d->image_width <= 0 || d->image_height <= 0) return oc_fail(MCC_EINVAL, w + ": the image size must be positive");
-    if (d->view_off[0] < 0) return oc_fail(MCC_EINVAL, w + ": view_off[0] is negative");
-    for (int v = 0; v < d->n_views; ++v) {
-        const int n = d->view_off[v + 1] - d->view_off[v];
-        if (n < 0) return oc_fail(MCC_EINVAL, w + ": view_off is not monotone at view " + std::to_string(v));
-        if (n < 4 || n > mcc::kPcMaxCorners)
-            return oc_fail(MCC_EINVAL, w + ": view " + std::to_string(v) + " has " + std::to_string(n) +
-                                           " corners, 4 to " + std::to_string(mcc::kPcMaxCorners) + " are supported");
-    }
+    const int rc = pin_check_views(w, d->n_views, d->view_off, d->obj, &d->img, 1, d->image_width, d->image_height);
+    if (rc) return rc;
     *planar = true;
     for (int i = d->view_off[0]; i < d->view_off[d->n_views]; ++i)
         if (d->obj[3 * (size_t)i + 2] != 0.0) *planar = false;
@@ -104,11 +87,6 @@ void smallest_eigvec9(const double* A0, double* h) {
     for (int k = 1; k < n; ++k)
         if (A[k * n + k] < A[im * n + im]) im = k;
     for (int k = 0; k < n; ++k) h[k] = V[k * n + im];
-}
-
-void mul3(const double* A, const double* B, double* C) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
 }
 
 // H [X Y 1]^T ~ [u v 1]^T by the normalised DLT (host/pnp.cpp::homography's form, on pixels)
@@ -181,18 +159,10 @@ int pc_init_matrix(const char* who, const mcc_calib_desc* d, double aspect, doub
         fy = (fx + fy) / (aspect + 1.0);
         fx = aspect * fy;
     }
-    const double Kn[9] = {fx, 0, cx, 0, fy, cy, 0, 0, 1};
-    std::memcpy(K, Kn, sizeof Kn);
+    const double g[4] = {fx, fy, cx, cy};
+    pin_matrix(g, K);
     return MCC_OK;
 }
-
-struct PcEvents {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~PcEvents() {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
 
 }  // namespace
 
@@ -219,9 +189,7 @@ extern "C" int mcc_calibrate_camera(const mcc_calib_desc* d, double* K, double* 
     if (rc) return rc;
     int m[mcc::kPcGlob];
     if ((rc = pc_mask("calibrate_camera", d->flags, d->nd, m))) return rc;
-    if (d->crit_type < 1 || d->crit_type > 3) return oc_fail(MCC_EINVAL, "calibrate_camera: crit_type must be 1, 2 or 3");
-    if ((d->crit_type & MCC_CRIT_COUNT) && d->max_count < 1)
-        return oc_fail(MCC_EINVAL, "calibrate_camera: max_count must be positive");
+    if ((rc = pin_check_criteria("calibrate_camera", d->crit_type, d->max_count))) return rc;
     const int flags = d->flags, nd = d->nd, n = d->n_views;
     const bool guess = flags & MCC_CALIB_USE_INTRINSIC_GUESS;
     if (!planar && !guess)
@@ -237,131 +205,44 @@ extern "C" int mcc_calibrate_camera(const mcc_calib_desc* d, double* K, double* 
     // ---- the start: g = fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6
     double g[mcc::kPcGlob] = {0};
     if (guess) {
-        g[0] = K[0]; g[1] = K[4]; g[2] = K[2]; g[3] = K[5];
-        for (int k = 0; k < nd; ++k) g[4 + k] = D[k];
+        pin_pack(K, D, nd, g);
     } else {
         double K0[9];
         if ((rc = pc_init_matrix("calibrate_camera", d, aspect, K0))) return rc;
-        g[0] = K0[0]; g[1] = K0[4]; g[2] = K0[2]; g[3] = K0[5];   // the distortion starts at 0
+        pin_pack(K0, nullptr, 0, g);   // the distortion starts at 0
     }
-    if (flags & MCC_CALIB_ZERO_TANGENT_DIST) g[6] = g[7] = 0.0;
-    if (nd == 4) g[8] = 0.0;
-    if (aspect > 0) g[0] = aspect * g[1];
+    pin_start_edits(flags, nd, aspect, g);
     int mask = 0;
     for (int k = 0; k < mcc::kPcGlob; ++k) mask |= m[k] << k;
 
     // ---- pose seeds
-    const double Ks[9] = {g[0], 0, g[2], 0, g[1], g[3], 0, 0, 1};
-    std::vector<double> x0(6 * (size_t)n);
-    {
-        std::vector<double> r(3 * (size_t)n), t(3 * (size_t)n), e((size_t)n);
-        std::vector<int> st((size_t)n);
-        mcc_pnp_desc pd{};
-        pd.n_views = n;
-        pd.view_off = d->view_off;
-        pd.obj = d->obj;
-        pd.img = d->img;
-        pd.n_cams = 1;
-        pd.K = Ks;
-        pd.D = g + 4;
-        pd.nd = 8;
-        pd.max_iter = 50;
-        pd.device = d->device;
-        if ((rc = mcc_solve_pnp_batch(&pd, r.data(), t.data(), e.data(), st.data(), nullptr))) return rc;
-        for (int v = 0; v < n; ++v) {
-            if (st[v] != MCC_PNP_SOLVED)
-                return oc_fail(MCC_EINVAL, "calibrate_camera: no pose seed for view " + std::to_string(v) +
-                                               " (solvePnP status " + std::to_string(st[v]) + ")");
-            for (int k = 0; k < 3; ++k) {
-                x0[6 * (size_t)v + k] = r[3 * (size_t)v + k];
-                x0[6 * (size_t)v + 3 + k] = t[3 * (size_t)v + k];
-            }
-        }
-    }
+    std::vector<double> r0(3 * (size_t)n), t0(3 * (size_t)n);
+    double* const rp = r0.data();
+    double* const tp = t0.data();
+    if ((rc = pin_seed_poses("calibrate_camera", n, d->view_off, d->obj, &d->img, 1, g, d->device, &rp, &tp))) return rc;
 
-    // ---- device buffers
-    const size_t first = (size_t)d->view_off[0], corners = (size_t)d->view_off[n] - first;
-    std::vector<int> off((size_t)n + 1);
-    for (int v = 0; v <= n; ++v) off[v] = d->view_off[v] - d->view_off[0];
-    const int group_size = std::max(1, (int)std::ceil(std::sqrt((double)n)));
-    const int n_groups = (n + group_size - 1) / group_size;
-    OCCHK(hipSetDevice(d->device));
-    DBuf<int> d_off, d_cnt;
-    DBuf<double> d_obj, d_img, d_x, d_xt, d_glob, d_dc, d_lin, d_Yz, d_contrib, d_gsum, d_esq, d_esq_t, d_egs;
-    DBuf<mcc::PcState> d_st;
-    OCCHK(d_off.upload(off.data(), off.size()));
-    OCCHK(d_obj.upload(d->obj + 3 * first, 3 * corners));
-    OCCHK(d_img.upload(d->img + 2 * first, 2 * corners));
-    OCCHK(d_x.upload(x0.data(), x0.size()));
-    OCCHK(d_xt.alloc(6 * (size_t)n));
-    OCCHK(d_glob.upload(g, mcc::kPcGlob));
-    OCCHK(d_dc.alloc(mcc::kPcGlob));
-    OCCHK(d_lin.alloc((size_t)n * mcc::kPcLinN));
-    OCCHK(d_Yz.alloc((size_t)n * mcc::kPcYz));
-    OCCHK(d_contrib.alloc((size_t)n * mcc::kPcCtrN));
-    OCCHK(d_gsum.alloc((size_t)n_groups * mcc::kPcCtrN));
-    OCCHK(d_esq.alloc((size_t)n));
-    OCCHK(d_esq_t.alloc((size_t)n));
-    OCCHK(d_egs.alloc((size_t)n_groups));
-    OCCHK(d_cnt.alloc(2 * ((size_t)n_groups + 1)));
-    OCCHK(hipMemset(d_cnt.p, 0, sizeof(int) * 2 * ((size_t)n_groups + 1)));
-    mcc::PcState s{};
-    s.init = 1;
-    s.relin = 1;
-    s.crit_type = d->crit_type;
-    s.max_count = (d->crit_type & MCC_CRIT_COUNT) ? d->max_count : kEpsOnlyCount;
-    if (!(d->crit_type & MCC_CRIT_COUNT)) s.crit_type |= MCC_CRIT_COUNT;
-    s.eps = d->eps;
-    s.lambda = 1e-3;
-    OCCHK(d_st.upload(&s, 1));
-    const mcc::PcArgs a{n, d_off.p, d_obj.p, d_img.p, mask, aspect, d_x.p, d_xt.p, d_glob.p, d_dc.p, d_lin.p, d_Yz.p,
-                        d_contrib.p, d_gsum.p, d_esq.p, d_esq_t.p, d_egs.p, d_cnt.p, d_st.p, group_size, n_groups};
-
-    // ---- the loop: at most ten rejections per accepted step, so 11 max_count trials in all
-    PcEvents e;
-    OCCHK(hipEventCreate(&e.ev[0]));
-    OCCHK(hipEventCreate(&e.ev[1]));
-    OCCHK(hipEventRecord(e.ev[0], nullptr));
-    OCCHK(mcc_launch_pc_try(a, nullptr));   // the error of the start
-    const long long cap = 11LL * s.max_count;
-    for (long long launched = 0; launched < cap;) {
-        for (int b = 0; b < kTrialBatch && launched < cap; ++b, ++launched) {
-            OCCHK(mcc_launch_pc_lin(a, nullptr));
-            OCCHK(mcc_launch_pc_try(a, nullptr));
-        }
-        OCCHK(hipMemcpy(&s, d_st.p, sizeof s, hipMemcpyDeviceToHost));
-        if (s.done) break;
-    }
-    OCCHK(hipEventRecord(e.ev[1], nullptr));
-    OCCHK(hipEventSynchronize(e.ev[1]));
-    OCCHK(hipMemcpy(&s, d_st.p, sizeof s, hipMemcpyDeviceToHost));
-    if (d->trials) *d->trials = s.trials;
-    if (device_ms) {
-        float ms = 0.f;
-        OCCHK(hipEventElapsedTime(&ms, e.ev[0], e.ev[1]));
-        *device_ms = (double)ms;
-    }
-    if (s.status == mcc::kPcNotFinite)
-        return oc_fail(MCC_EINVAL, "calibrate_camera: the reprojection error of the start is not finite");
-    if (!s.done) return oc_fail(MCC_EINVAL, "calibrate_camera: the loop did not terminate");
+    // ---- the loop
+    PinLoop lp;
+    const PinShape shape{mcc::kPcGlob, mcc::kPcLinN, mcc::kPcYz, mcc::kPcCtrN, 1};
+    if ((rc = lp.init(d->device, n, d->view_off, d->obj, &d->img, rp, tp, g, shape, d->crit_type, d->max_count, d->eps)))
+        return rc;
+    mcc::PcArgs a{};
+    lp.fill(a);
+    a.img = lp.img[0].p;
+    a.mask = mask;
+    a.aspect = aspect;
+    if ((rc = lp.run("calibrate_camera", [&] { return mcc_launch_pc_lin(a, nullptr); },
+                     [&] { return mcc_launch_pc_try(a, nullptr); }, d->trials, device_ms)))
+        return rc;
 
     // ---- results
     std::vector<double> esq((size_t)n);
-    OCCHK(hipMemcpy(x0.data(), d_x.p, sizeof(double) * x0.size(), hipMemcpyDeviceToHost));
-    OCCHK(hipMemcpy(g, d_glob.p, sizeof g, hipMemcpyDeviceToHost));
-    OCCHK(hipMemcpy(esq.data(), d_esq.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    const double Kn[9] = {g[0], 0, g[2], 0, g[1], g[3], 0, 0, 1};
-    std::memcpy(K, Kn, sizeof Kn);
-    for (int k = 0; k < nd; ++k) D[k] = g[4 + k];
-    for (int v = 0; v < n; ++v) {
-        for (int k = 0; k < 3; ++k) {
-            if (rvec) rvec[3 * (size_t)v + k] = x0[6 * (size_t)v + k];
-            if (tvec) tvec[3 * (size_t)v + k] = x0[6 * (size_t)v + 3 + k];
-        }
-        if (view_rms) view_rms[v] = std::sqrt(esq[v] / (double)(off[v + 1] - off[v]));
-    }
-    if (rms) *rms = std::sqrt(s.err / (double)corners);
-    if (iterations) *iterations = s.iter;
-    if (status) *status = s.status;
+    if ((rc = lp.download(g, rvec, tvec, esq.data()))) return rc;
+    pin_unpack(g, nd, K, D);
+    if (view_rms)
+        for (int v = 0; v < n; ++v) view_rms[v] = std::sqrt(esq[v] / (double)(lp.off[v + 1] - lp.off[v]));
+    if (rms) *rms = std::sqrt(lp.s.err / (double)lp.corners);
+    if (iterations) *iterations = lp.s.iter;
+    if (status) *status = lp.s.status;
     return MCC_OK;
 }

@@ -1,6 +1,7 @@
 // mcc_pincalib_internal.h -- device state and kernel arguments of the pinhole calibrateCamera
-// (mcc_calibrate_camera, include/mcc.h), shared by mcc_pincalib.hip and mcc_pincalib_api.cpp.  Not
-// part of the public ABI.
+// (mcc_calibrate_camera, include/mcc.h), shared by mcc_pincalib.hip and mcc_pincalib_api.cpp, and the
+// loop state and Levenberg-Marquardt policy that the pinhole stereoCalibrate shares with it
+// (mcc_pinloop_device.hpp, mcc_pinloop_host.hpp).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,6 +34,40 @@ struct PcState {
     double err;      // sum of squared residuals at the current parameters
     double change;   // |x_new - x_old| / |x_old| of the last accepted step
 };
+
+// The Levenberg-Marquardt policy, once, for both pinhole loops (pin_verdict, mcc_pinloop_device.hpp) and
+// for the host (tests/cpp/test_pinloop_policy.cpp): lambda starts at 1e-3 (the host sets it), a trial is
+// accepted when its factorisation held and en <= err (so a NaN error is a rejection), lambda / 10 floored at
+// 1e-12 on an acceptance and x 10 on a rejection, ten rejections in a row end the loop as stalled.
+__host__ __device__ inline bool pc_accepts(const PcState& s, double en) { return !s.fail && en <= s.err; }
+
+// The state after k_*_try's sum en of the trial's squared error: the evaluation of the start (s.init), a
+// rejection or an acceptance, with the `done` / `status` they set.  `change` is read on an acceptance only.
+__host__ __device__ inline PcState pc_next(PcState s, double en, double change) {
+    if (s.init) {
+        s.err = en;
+        s.init = 0;
+        s.relin = 1;
+        if (!(fabs(en) < 1.7e308)) { s.done = 1; s.status = kPcNotFinite; }
+    } else if (!pc_accepts(s, en)) {
+        s.trials = s.trials + 1;
+        s.lambda = s.lambda * 10.0;
+        s.relin = 0;
+        if (s.tries + 1 >= 10) { s.done = 1; s.status = kPcStalled; }
+        s.tries = s.tries + 1;
+    } else {
+        s.trials = s.trials + 1;
+        s.tries = 0;
+        s.relin = 1;
+        s.err = en;
+        s.change = change;
+        s.lambda = fmax(s.lambda * 0.1, 1e-12);
+        if ((s.crit_type & 2) && change < s.eps) { s.done = 1; s.status = kPcConverged; }
+        else if ((s.crit_type & 1) && s.iter + 1 >= s.max_count) { s.done = 1; s.status = kPcCount; }
+        s.iter = s.iter + 1;
+    }
+    return s;
+}
 
 struct PcArgs {
     int n;                       // views

@@ -57,11 +57,6 @@ int pr_p3(const double* P, int ld, const double* none, double* out) {
     return MCC_OK;
 }
 
-void pr_mul(const double* A, const double* B, double* C) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
-}
-
 // the host part of initUndistortRectifyMap: everything k_pr_map takes but the maps
 int pr_map_args(const double* K, const double* D, int nd, const double* R, const double* P, int ld, int w, int h,
                 mcc::PrMapArgs* a, bool* rational) {
@@ -70,32 +65,13 @@ int pr_map_args(const double* K, const double* D, int nd, const double* R, const
     if ((rc = or_check_size(w, h, "map"))) return rc;
     double PP[9], PR[9];
     if ((rc = pr_p3(P, ld, K, PP))) return rc;
-    pr_mul(PP, R ? R : kEye, PR);
+    mul3(PP, R ? R : kEye, PR);
     if (!inv3(PR, a->iPR)) return oc_fail(MCC_EINVAL, "P R is singular");
     a->w = w;
     a->h = h;
     *rational = a->cam.k4 != 0.0 || a->cam.k5 != 0.0 || a->cam.k6 != 0.0;
     return MCC_OK;
 }
-
-struct PrEvents {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~PrEvents() {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    hipError_t create() {
-        hipError_t e = hipEventCreate(&ev[0]);
-        return e == hipSuccess ? hipEventCreate(&ev[1]) : e;
-    }
-    hipError_t elapsed(double* ms) {
-        hipError_t e = hipEventSynchronize(ev[1]);
-        float f = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&f, ev[0], ev[1]);
-        *ms = f;
-        return e;
-    }
-};
 
 int pr_alloc(mcc_pinrect* h) {
     OCCHK(hipSetDevice(h->device));
@@ -195,7 +171,7 @@ int mcc_undistort_points(int n, const double* src, const double* K, const double
     OCCHK(out.alloc(2 * (size_t)n));
     a.src = in.p;
     a.dst = out.p;
-    PrEvents ev;
+    OcEvents ev;
     OCCHK(ev.create());
     OCCHK(hipEventRecord(ev.ev[0], nullptr));
     OCCHK(mcc_launch_pr_points(a, nullptr));
@@ -225,7 +201,7 @@ int mcc_init_undistort_rectify_map(const double* K, const double* D, int nd, con
     OCCHK(m2.alloc(b2));
     a.map1 = m1.p;
     a.map2 = m2.p;
-    PrEvents ev;
+    OcEvents ev;
     OCCHK(ev.create());
     OCCHK(hipEventRecord(ev.ev[0], nullptr));
     OCCHK(mcc_launch_pr_map(a, map_type, rational, nullptr));
@@ -281,8 +257,8 @@ int mcc_stereo_rectify(const double* K1, const double* D1, const double* K2, con
     }
     double wR[9];
     rodrigues_host(ww, wR);
-    pr_mul(wR, rt, Rk[0]);
-    pr_mul(wR, r, Rk[1]);
+    mul3(wR, rt, Rk[0]);
+    mul3(wR, r, Rk[1]);
     for (int i = 0; i < 3; ++i) t[i] = Rk[1][3 * i] * T[0] + Rk[1][3 * i + 1] * T[1] + Rk[1][3 * i + 2] * T[2];
 
     // 2. the focal length: the smaller of the two across the baseline, shrunk for barrel distortion

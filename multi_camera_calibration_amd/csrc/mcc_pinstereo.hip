@@ -8,16 +8,20 @@
 //              coordinates (ps_assemble, mcc_pinstereo_device.hpp; after a rejected trial the stored arrow is
 //              reused), damps and eliminates the 6 x 6 pose block and writes the view's contribution to the
 //              reduced 30 x 30 system.  The contributions are summed in view order by the two-level
-//              last-arriver ticket; the last arriver solves the reduced system in LDS for the global step dc.
+//              last-arriver ticket (pin_reduce, mcc_pinloop_device.hpp); the last arriver solves the reduced
+//              system in LDS for the global step dc.
 //   k_ps_try   back-substitutes the view's pose step, evaluates both cameras' squared error of the trial
-//              parameters and sums it over the views the same way; the last arriver accepts or rejects the
-//              trial and runs the stop tests.  With st->init it only evaluates the starting point.
+//              parameters and sums it over the views the same way (pin_sum_err, two slots per view); the last
+//              arriver accepts or rejects the trial and runs the stop tests (pin_verdict; the policy is
+//              pc_next, mcc_pincalib_internal.h), reloading the 30 slots for its share of the step's norms.
+//              With st->init it only evaluates the starting point.
 // Everything the kernels index dynamically (the sums, the maps, the 30 x 30) is in LDS, never in a lane's
 // private arrays.  The loop state is PcState; a launch after `done` returns at once.
 #include <hip/hip_runtime.h>
 
 #include "mcc_omnicalib_device.hpp"
 #include "mcc_pinstereo_device.hpp"
+#include "mcc_pinloop_device.hpp"
 #include "mcc_pinstereo_internal.h"
 
 namespace mcc {
@@ -93,14 +97,8 @@ __global__ __launch_bounds__(64) void k_ps_lin(PsArgs a) {
     for (int i = lane; i < kPsYz; i += 64) a.Yz[(size_t)v * kPsYz + i] = Yz[i];
     for (int e = lane; e < PsCtr::N; e += 64) oc_st(a.contrib + (size_t)v * PsCtr::N + e, ctr[e]);
 
-    const int grp = v / a.group_size, g0 = grp * a.group_size, gn = min(a.group_size, a.n - g0);
-    if (!oc_arrive(&a.cnt[grp], gn)) return;
-    for (int e = lane; e < PsCtr::N; e += 64)
-        oc_st(a.gsum + (size_t)grp * PsCtr::N + e, oc_sum<PsCtr::N>(a.contrib + (size_t)g0 * PsCtr::N + e, gn));
-    if (!oc_arrive(&a.cnt[a.n_groups], a.n_groups)) return;
     double* tot = ctr;   // (the view's own contribution has left for global memory)
-    for (int e = lane; e < PsCtr::N; e += 64) tot[e] = oc_sum<PsCtr::N>(a.gsum + e, a.n_groups);
-    __syncthreads();
+    if (!pin_reduce<PsCtr::N>(a, v, lane, tot)) return;
     const bool ok = ps_reduced_solve(tot, lambda, a.mask, lane, M, b, dcs);
     if (lane < kPsG) a.dc[lane] = dcs[lane];
     if (lane == 0) st->fail = ok ? 0 : 1;
@@ -147,78 +145,25 @@ __global__ __launch_bounds__(64) void k_ps_try(PsArgs a) {
         oc_st(a.esq_t + 2 * (size_t)v, sq1);
         oc_st(a.esq_t + 2 * (size_t)v + 1, sq2);
     }
-    int* cnt = a.cnt + a.n_groups + 1;
-    const int grp = v / a.group_size, g0 = grp * a.group_size, gn = min(a.group_size, a.n - g0);
-    if (!oc_arrive(&cnt[grp], gn)) return;
-    {
-        const double gs = oc_sum<1>(a.esq_t + 2 * (size_t)g0, 2 * gn);
-        if (lane == 0) oc_st(a.egs + grp, gs);
-    }
-    if (!oc_arrive(&cnt[a.n_groups], a.n_groups)) return;
-    const double en = oc_sum<1>(a.egs, a.n_groups);
-
-    // ---- the last arriver: accept or reject, stop tests
-    const int iter = st->iter, tries = st->tries, trials = st->trials, fail = st->fail;
-    const int crit = st->crit_type, max_count = st->max_count;
-    const double eps = st->eps, lambda = st->lambda, err = st->err;
-    if (init) {
-        for (int i = lane; i < 2 * a.n; i += 64) a.esq[i] = oc_ld(a.esq_t + i);
-        if (lane == 0) {
-            st->err = en;
-            st->init = 0;
-            st->relin = 1;
-            if (!(fabs(en) < 1.7e308)) { st->done = 1; st->status = kPcNotFinite; }
-        }
-        return;
-    }
-    const bool accept = !fail && en <= err;   // (a NaN error is a rejection)
-    if (!accept) {
-        if (lane == 0) {
-            st->trials = trials + 1;
-            st->lambda = lambda * 10.0;
-            st->tries = tries + 1;
-            st->relin = 0;
-            if (tries + 1 >= 10) { st->done = 1; st->status = kPcStalled; }
-        }
-        return;
-    }
-    double dn = 0.0, xn = 0.0;
-    for (int i = lane; i < 6 * a.n; i += 64) {
-        const double xo = a.x[i], xw = oc_ld(a.xt + i), d = xw - xo;
-        dn += d * d;
-        xn += xo * xo;
-        a.x[i] = xw;
-    }
-    dn = pnp_wave_sum(dn);
-    xn = pnp_wave_sum(xn);
-    {   // the globals once more (the same bits), now that the passes over the corners are done with the registers
-        double g[kPsG], dc[kPsG];
-        ps_load_trial(a, 0, g, dc, gt);
+    double en;
+    if (!pin_sum_err<2>(a, v, lane, en)) return;
+    pin_verdict<2>(a, lane, init, en, [&](double& dn, double& xn) {
+        {   // the globals once more (the same bits), now that the passes over the corners are done with the registers
+            double g[kPsG], dc[kPsG];
+            ps_load_trial(a, 0, g, dc, gt);
 #pragma unroll
-        for (int k = 0; k < kPsG; ++k) {
-            const double d = gt[k] - g[k];
-            dn += d * d;
-            xn += g[k] * g[k];
+            for (int k = 0; k < kPsG; ++k) {
+                const double d = gt[k] - g[k];
+                dn += d * d;
+                xn += g[k] * g[k];
+            }
         }
-    }
-    pnp_wave_sync();   // every lane has read glob before lane 0 writes it
-    if (lane == 0) {
+        pnp_wave_sync();   // every lane has read glob before lane 0 writes it
+        if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < kPsG; ++k) a.glob[k] = gt[k];
-    }
-    for (int i = lane; i < 2 * a.n; i += 64) a.esq[i] = oc_ld(a.esq_t + i);
-    const double change = sqrt(dn) / sqrt(xn);
-    if (lane == 0) {
-        st->trials = trials + 1;
-        st->iter = iter + 1;
-        st->tries = 0;
-        st->relin = 1;
-        st->err = en;
-        st->change = change;
-        st->lambda = fmax(lambda * 0.1, 1e-12);
-        if ((crit & 2) && change < eps) { st->done = 1; st->status = kPcConverged; }
-        else if ((crit & 1) && iter + 1 >= max_count) { st->done = 1; st->status = kPcCount; }
-    }
+            for (int k = 0; k < kPsG; ++k) a.glob[k] = gt[k];
+        }
+    });
 }
 
 }  // namespace mcc

@@ -1,9 +1,9 @@
 // mcc_pinstereo_api.cpp -- host side of mcc_stereo_calibrate, mcc_stereo_calib_mask and
 // mcc_stereo_init_extrinsics (include/mcc.h).  The host checks the descriptor before any device call, finds
-// the start with the calls the library already has (one mcc_solve_pnp_batch over both cameras' views at the
-// given intrinsics, or two mcc_calibrate_camera), takes the rig's start from the views' medians and then only
-// launches trials (k_ps_lin + k_ps_try, mcc_pinstereo.hip) in batches, reading the device-resident loop state
-// between batches.  E and F are computed here from the result.
+// the start with the calls the library already has (one pose-seed batch over both cameras' views at the given
+// intrinsics, pin_seed_poses, or two mcc_calibrate_camera), takes the rig's start from the views' medians and
+// hands the loop to PinLoop (mcc_pinloop_host.hpp) with its two launches, k_ps_lin and k_ps_try
+// (mcc_pinstereo.hip).  E and F are computed here from the result.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,19 +13,13 @@
 #include <vector>
 
 #include "../../include/mcc.h"
-#include "mcc_omnicalib_host.hpp"
+#include "mcc_pinloop_host.hpp"
 #include "mcc_pinstereo_internal.h"
 
 namespace {
 
-constexpr int kCameraFlags = MCC_CALIB_USE_INTRINSIC_GUESS | MCC_CALIB_FIX_ASPECT_RATIO | MCC_CALIB_FIX_PRINCIPAL_POINT |
-                             MCC_CALIB_ZERO_TANGENT_DIST | MCC_CALIB_FIX_FOCAL_LENGTH | MCC_CALIB_FIX_K1 |
-                             MCC_CALIB_FIX_K2 | MCC_CALIB_FIX_K3 | MCC_CALIB_FIX_K4 | MCC_CALIB_FIX_K5 |
-                             MCC_CALIB_FIX_K6 | MCC_CALIB_RATIONAL_MODEL;
-constexpr int kKnownFlags = kCameraFlags | MCC_CALIB_FIX_INTRINSIC | MCC_CALIB_SAME_FOCAL_LENGTH |
+constexpr int kKnownFlags = kPinCameraFlags | MCC_CALIB_FIX_INTRINSIC | MCC_CALIB_SAME_FOCAL_LENGTH |
                             MCC_CALIB_USE_EXTRINSIC_GUESS;
-constexpr int kTrialBatch = 8;       // trials enqueued between two reads of the state
-constexpr int kEpsOnlyCount = 1000;  // accepted steps at most when the criteria have no count
 constexpr int kG = mcc::kPsGlob, kCam1 = 6, kCam2 = 18;
 
 int ps_mask(const char* who, int flags, int nd, int* m, int* tie) {
@@ -33,7 +27,7 @@ int ps_mask(const char* who, int flags, int nd, int* m, int* tie) {
         return oc_fail(MCC_EINVAL, std::string(who) + ": unsupported flag bits " + std::to_string(flags & ~kKnownFlags));
     if (nd != 4 && nd != 5 && nd != 8) return oc_fail(MCC_EINVAL, std::string(who) + ": nd must be 4, 5 or 8");
     int cam[mcc::kPcGlob];
-    const int rc = mcc_calib_mask(flags & kCameraFlags, nd, cam);
+    const int rc = mcc_calib_mask(flags & kPinCameraFlags, nd, cam);
     if (rc) return rc;
     for (int k = 0; k < kG; ++k) {
         m[k] = k < kCam1 ? 1 : cam[(k - kCam1) % mcc::kPcGlob];
@@ -53,11 +47,6 @@ int ps_mask(const char* who, int flags, int nd, int* m, int* tie) {
         if (!(flags & MCC_CALIB_FIX_ASPECT_RATIO)) tie[kCam2] = kCam1;
     }
     return MCC_OK;
-}
-
-void mul3(const double* A, const double* B, double* C) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
 }
 
 // the rotation vector of R: the angle from atan2(s, c); the axis from the skew part, or within 1e-5 rad of pi
@@ -178,14 +167,6 @@ void same_focal_start(double* g, const double* aspect) {
         if (aspect[c] > 0) g[kCam1 + mcc::kPcGlob * c] = aspect[c] * g[kCam1 + mcc::kPcGlob * c + 1];
 }
 
-struct PsEvents {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~PsEvents() {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 }  // namespace
 
 extern "C" int mcc_stereo_calib_mask(int flags, int nd, int* mask, int* tie) {
@@ -216,21 +197,13 @@ extern "C" int mcc_stereo_calibrate(const mcc_stereo_calib_desc* d, double* K1, 
                                     double* rms, int* iterations, int* status, double* device_ms) {
     const std::string w = "stereo_calibrate";
     if (!d || !K1 || !D1 || !K2 || !D2) return oc_fail(MCC_EINVAL, w + ": null argument");
-    if (d->n_views < 1) return oc_fail(MCC_EINVAL, w + ": n_views must be positive");
-    if (!d->view_off || !d->obj || !d->img1 || !d->img2) return oc_fail(MCC_EINVAL, w + ": null pointer in the descriptor");
-    if (d->image_width <= 0 || d->image_height <= 0) return oc_fail(MCC_EINVAL, w + ": the image size must be positive");
-    if (d->view_off[0] < 0) return oc_fail(MCC_EINVAL, w + ": view_off[0] is negative");
+    const double* const img[2] = {d->img1, d->img2};
+    int rc = pin_check_views(w, d->n_views, d->view_off, d->obj, img, 2, d->image_width, d->image_height);
+    if (rc) return rc;
     const int n = d->n_views, flags = d->flags, nd = d->nd;
-    for (int v = 0; v < n; ++v) {
-        const int c = d->view_off[v + 1] - d->view_off[v];
-        if (c < 4 || c > mcc::kPcMaxCorners)
-            return oc_fail(MCC_EINVAL, w + ": view " + std::to_string(v) + " has " + std::to_string(c) + " corners, 4 to " +
-                                           std::to_string(mcc::kPcMaxCorners) + " are supported");
-    }
-    int m[kG], tie[kG], rc;
+    int m[kG], tie[kG];
     if ((rc = ps_mask("stereo_calibrate", flags, nd, m, tie))) return rc;
-    if (d->crit_type < 1 || d->crit_type > 3) return oc_fail(MCC_EINVAL, w + ": crit_type must be 1, 2 or 3");
-    if ((d->crit_type & MCC_CRIT_COUNT) && d->max_count < 1) return oc_fail(MCC_EINVAL, w + ": max_count must be positive");
+    if ((rc = pin_check_criteria(w, d->crit_type, d->max_count))) return rc;
     const bool fixi = flags & MCC_CALIB_FIX_INTRINSIC, guess = flags & MCC_CALIB_USE_INTRINSIC_GUESS;
     const bool same = !fixi && (flags & MCC_CALIB_SAME_FOCAL_LENGTH);
     if ((flags & MCC_CALIB_USE_EXTRINSIC_GUESS) && (!R || !T))
@@ -251,78 +224,30 @@ extern "C" int mcc_stereo_calibrate(const mcc_stereo_calib_desc* d, double* K1, 
     }
 
     // ---- the start: the cameras' slots and both cameras' pose of every view
-    const size_t first = (size_t)d->view_off[0], corners = (size_t)d->view_off[n] - first;
-    std::vector<int> off((size_t)n + 1);
-    for (int v = 0; v <= n; ++v) off[v] = d->view_off[v] - d->view_off[0];
-    const double* img[2] = {d->img1 + 2 * first, d->img2 + 2 * first};
     double g[kG] = {0};
     std::vector<double> rv[2], tv[2];
     for (auto& a : rv) a.resize(3 * (size_t)n);
     for (auto& a : tv) a.resize(3 * (size_t)n);
+    double* const rp[2] = {rv[0].data(), rv[1].data()};
+    double* const tp[2] = {tv[0].data(), tv[1].data()};
     if (fixi || guess) {
         for (int c = 0; c < 2; ++c) {
             double* gc = g + kCam1 + mcc::kPcGlob * c;
-            gc[0] = Kc[c][0]; gc[1] = Kc[c][4]; gc[2] = Kc[c][2]; gc[3] = Kc[c][5];
-            for (int k = 0; k < nd; ++k) gc[4 + k] = Dc[c][k];
-            if (!fixi) {
-                if (flags & MCC_CALIB_ZERO_TANGENT_DIST) gc[6] = gc[7] = 0.0;
-                if (nd == 4) gc[8] = 0.0;
-                if (aspect[c] > 0) gc[0] = aspect[c] * gc[1];
-            }
+            pin_pack(Kc[c], Dc[c], nd, gc);
+            if (!fixi) pin_start_edits(flags, nd, aspect[c], gc);
         }
         if (same) same_focal_start(g, aspect);   // (before the seeds, so that they are the poses at the start itself)
-        // one solvePnP batch over 2 n views: camera 1's, then camera 2's
-        std::vector<int> off2(2 * (size_t)n + 1), cam(2 * (size_t)n);
-        std::vector<double> obj2(6 * corners), img2(4 * corners), Ks(18), Ds(16), r(6 * (size_t)n), t(6 * (size_t)n),
-            e(2 * (size_t)n);
-        std::vector<int> st(2 * (size_t)n);
-        for (int c = 0; c < 2; ++c) {
-            const double* gc = g + kCam1 + mcc::kPcGlob * c;
-            const double Kn[9] = {gc[0], 0, gc[2], 0, gc[1], gc[3], 0, 0, 1};
-            std::memcpy(&Ks[9 * c], Kn, sizeof Kn);
-            std::memcpy(&Ds[8 * c], gc + 4, 8 * sizeof(double));
-            std::memcpy(&obj2[3 * corners * c], d->obj + 3 * first, 3 * corners * sizeof(double));
-            std::memcpy(&img2[2 * corners * c], img[c], 2 * corners * sizeof(double));
-            for (int v = 0; v < n; ++v) {
-                off2[(size_t)c * n + v] = (int)(corners * c) + off[v];
-                cam[(size_t)c * n + v] = c;
-            }
-        }
-        off2[2 * (size_t)n] = (int)(2 * corners);
-        mcc_pnp_desc pd{};
-        pd.n_views = 2 * n;
-        pd.view_off = off2.data();
-        pd.obj = obj2.data();
-        pd.img = img2.data();
-        pd.view_cam = cam.data();
-        pd.n_cams = 2;
-        pd.K = Ks.data();
-        pd.D = Ds.data();
-        pd.nd = 8;
-        pd.max_iter = 50;
-        pd.device = d->device;
-        if ((rc = mcc_solve_pnp_batch(&pd, r.data(), t.data(), e.data(), st.data(), nullptr))) return rc;
-        for (int c = 0; c < 2; ++c)
-            for (int v = 0; v < n; ++v) {
-                const size_t i = (size_t)c * n + v;
-                if (st[i] != MCC_PNP_SOLVED)
-                    return oc_fail(MCC_EINVAL, w + ": no pose seed for view " + std::to_string(v) + " in camera " +
-                                                   std::to_string(c + 1) + " (solvePnP status " + std::to_string(st[i]) + ")");
-                for (int k = 0; k < 3; ++k) {
-                    rv[c][3 * (size_t)v + k] = r[3 * i + k];
-                    tv[c][3 * (size_t)v + k] = t[3 * i + k];
-                }
-            }
+        if ((rc = pin_seed_poses(w, n, d->view_off, d->obj, img, 2, g + kCam1, d->device, rp, tp))) return rc;
     } else {
         for (int c = 0; c < 2; ++c) {
             mcc_calib_desc cd{};
             cd.n_views = n;
-            cd.view_off = off.data();
-            cd.obj = d->obj + 3 * first;
+            cd.view_off = d->view_off;
+            cd.obj = d->obj;
             cd.img = img[c];
             cd.image_width = d->image_width;
             cd.image_height = d->image_height;
-            cd.flags = flags & kCameraFlags;
+            cd.flags = flags & kPinCameraFlags;
             cd.nd = nd;
             cd.crit_type = d->crit_type;
             cd.max_count = d->max_count;
@@ -330,11 +255,9 @@ extern "C" int mcc_stereo_calibrate(const mcc_stereo_calib_desc* d, double* K1, 
             cd.device = d->device;
             double Kt[9], Dt[8] = {0};
             std::memcpy(Kt, Kc[c], sizeof Kt);
-            if ((rc = mcc_calibrate_camera(&cd, Kt, Dt, rv[c].data(), tv[c].data(), nullptr, nullptr, nullptr, nullptr, nullptr)))
+            if ((rc = mcc_calibrate_camera(&cd, Kt, Dt, rp[c], tp[c], nullptr, nullptr, nullptr, nullptr, nullptr)))
                 return oc_fail(rc, w + ": camera " + std::to_string(c + 1) + ": " + mcc_last_error());
-            double* gc = g + kCam1 + mcc::kPcGlob * c;
-            gc[0] = Kt[0]; gc[1] = Kt[4]; gc[2] = Kt[2]; gc[3] = Kt[5];
-            for (int k = 0; k < nd; ++k) gc[4 + k] = Dt[k];
+            pin_pack(Kt, Dt, nd, g + kCam1 + mcc::kPcGlob * c);
         }
         if (same) same_focal_start(g, aspect);
     }
@@ -343,111 +266,46 @@ extern "C" int mcc_stereo_calibrate(const mcc_stereo_calib_desc* d, double* K1, 
         log_host(R, g);
         for (int k = 0; k < 3; ++k) g[3 + k] = T[k];
     } else {
-        init_extrinsics(n, rv[0].data(), tv[0].data(), rv[1].data(), tv[1].data(), g, g + 3);
+        init_extrinsics(n, rp[0], tp[0], rp[1], tp[1], g, g + 3);
     }
     for (int k = 0; k < 6; ++k)
         if (!std::isfinite(g[k])) return oc_fail(MCC_EINVAL, w + ": the rig's start is not finite");
-    std::vector<double> x0(6 * (size_t)n);
-    for (int v = 0; v < n; ++v)
-        for (int k = 0; k < 3; ++k) {
-            x0[6 * (size_t)v + k] = rv[0][3 * (size_t)v + k];
-            x0[6 * (size_t)v + 3 + k] = tv[0][3 * (size_t)v + k];
-        }
     int mask = 0;
     for (int k = 0; k < kG; ++k) mask |= m[k] << k;
 
-    // ---- device buffers
-    const int group_size = std::max(1, (int)std::ceil(std::sqrt((double)n)));
-    const int n_groups = (n + group_size - 1) / group_size;
-    OCCHK(hipSetDevice(d->device));
-    DBuf<int> d_off, d_cnt;
-    DBuf<double> d_obj, d_img1, d_img2, d_x, d_xt, d_glob, d_dc, d_lin, d_Yz, d_contrib, d_gsum, d_esq, d_esq_t, d_egs;
-    DBuf<mcc::PcState> d_st;
-    OCCHK(d_off.upload(off.data(), off.size()));
-    OCCHK(d_obj.upload(d->obj + 3 * first, 3 * corners));
-    OCCHK(d_img1.upload(img[0], 2 * corners));
-    OCCHK(d_img2.upload(img[1], 2 * corners));
-    OCCHK(d_x.upload(x0.data(), x0.size()));
-    OCCHK(d_xt.alloc(6 * (size_t)n));
-    OCCHK(d_glob.upload(g, kG));
-    OCCHK(d_dc.alloc(kG));
-    OCCHK(d_lin.alloc((size_t)n * mcc::kPsLinN));
-    OCCHK(d_Yz.alloc((size_t)n * mcc::kPsYz));
-    OCCHK(d_contrib.alloc((size_t)n * mcc::kPsCtrN));
-    OCCHK(d_gsum.alloc((size_t)n_groups * mcc::kPsCtrN));
-    OCCHK(d_esq.alloc(2 * (size_t)n));
-    OCCHK(d_esq_t.alloc(2 * (size_t)n));
-    OCCHK(d_egs.alloc((size_t)n_groups));
-    OCCHK(d_cnt.alloc(2 * ((size_t)n_groups + 1)));
-    OCCHK(hipMemset(d_cnt.p, 0, sizeof(int) * 2 * ((size_t)n_groups + 1)));
-    mcc::PcState s{};
-    s.init = 1;
-    s.relin = 1;
-    s.crit_type = d->crit_type;
-    s.max_count = (d->crit_type & MCC_CRIT_COUNT) ? d->max_count : kEpsOnlyCount;
-    if (!(d->crit_type & MCC_CRIT_COUNT)) s.crit_type |= MCC_CRIT_COUNT;
-    s.eps = d->eps;
-    s.lambda = 1e-3;
-    OCCHK(d_st.upload(&s, 1));
-    const mcc::PsArgs a{n, d_off.p, d_obj.p, d_img1.p, d_img2.p, mask, same ? 1 : 0, aspect[0], aspect[1], d_x.p, d_xt.p,
-                        d_glob.p, d_dc.p, d_lin.p, d_Yz.p, d_contrib.p, d_gsum.p, d_esq.p, d_esq_t.p, d_egs.p, d_cnt.p,
-                        d_st.p, group_size, n_groups};
-
-    // ---- the loop: at most ten rejections per accepted step, so 11 max_count trials in all
-    PsEvents ev;
-    OCCHK(hipEventCreate(&ev.ev[0]));
-    OCCHK(hipEventCreate(&ev.ev[1]));
-    OCCHK(hipEventRecord(ev.ev[0], nullptr));
-    OCCHK(mcc_launch_ps_try(a, nullptr));   // the error of the start
-    const long long cap = 11LL * s.max_count;
-    for (long long launched = 0; launched < cap;) {
-        for (int b = 0; b < kTrialBatch && launched < cap; ++b, ++launched) {
-            OCCHK(mcc_launch_ps_lin(a, nullptr));
-            OCCHK(mcc_launch_ps_try(a, nullptr));
-        }
-        OCCHK(hipMemcpy(&s, d_st.p, sizeof s, hipMemcpyDeviceToHost));
-        if (s.done) break;
-    }
-    OCCHK(hipEventRecord(ev.ev[1], nullptr));
-    OCCHK(hipEventSynchronize(ev.ev[1]));
-    OCCHK(hipMemcpy(&s, d_st.p, sizeof s, hipMemcpyDeviceToHost));
-    if (d->trials) *d->trials = s.trials;
-    if (device_ms) {
-        float ms = 0.f;
-        OCCHK(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]));
-        *device_ms = (double)ms;
-    }
-    if (s.status == mcc::kPcNotFinite) return oc_fail(MCC_EINVAL, w + ": the reprojection error of the start is not finite");
-    if (!s.done) return oc_fail(MCC_EINVAL, w + ": the loop did not terminate");
+    // ---- the loop
+    PinLoop lp;
+    const PinShape shape{kG, mcc::kPsLinN, mcc::kPsYz, mcc::kPsCtrN, 2};
+    if ((rc = lp.init(d->device, n, d->view_off, d->obj, img, rp[0], tp[0], g, shape, d->crit_type, d->max_count, d->eps)))
+        return rc;
+    mcc::PsArgs a{};
+    lp.fill(a);
+    a.img1 = lp.img[0].p;
+    a.img2 = lp.img[1].p;
+    a.mask = mask;
+    a.same = same ? 1 : 0;
+    a.aspect1 = aspect[0];
+    a.aspect2 = aspect[1];
+    if ((rc = lp.run(w, [&] { return mcc_launch_ps_lin(a, nullptr); }, [&] { return mcc_launch_ps_try(a, nullptr); }, d->trials,
+                     device_ms)))
+        return rc;
 
     // ---- results
     std::vector<double> esq(2 * (size_t)n);
-    OCCHK(hipMemcpy(x0.data(), d_x.p, sizeof(double) * x0.size(), hipMemcpyDeviceToHost));
-    OCCHK(hipMemcpy(g, d_glob.p, sizeof g, hipMemcpyDeviceToHost));
-    OCCHK(hipMemcpy(esq.data(), d_esq.p, sizeof(double) * esq.size(), hipMemcpyDeviceToHost));
-    for (int c = 0; c < 2; ++c) {
-        const double* gc = g + kCam1 + mcc::kPcGlob * c;
-        const double Kn[9] = {gc[0], 0, gc[2], 0, gc[1], gc[3], 0, 0, 1};
-        if (!fixi) {   // (fixed intrinsics are not rewritten: they stay the caller's bits, K's off-diagonals included)
-            std::memcpy(Kc[c], Kn, sizeof Kn);
-            for (int k = 0; k < nd; ++k) Dc[c][k] = gc[4 + k];
-        }
-    }
+    if ((rc = lp.download(g, rvec, tvec, esq.data()))) return rc;
+    if (!fixi)   // (fixed intrinsics are not rewritten: they stay the caller's bits, K's off-diagonals included)
+        for (int c = 0; c < 2; ++c) pin_unpack(g + kCam1 + mcc::kPcGlob * c, nd, Kc[c], Dc[c]);
     double Rh[9];
     rodrigues_host(g, Rh);
     if (R) std::memcpy(R, Rh, sizeof Rh);
     if (T) std::memcpy(T, g + 3, 3 * sizeof(double));
     essential_fundamental(Rh, g + 3, g + kCam1, g + kCam2, E, F);
-    for (int v = 0; v < n; ++v) {
-        for (int k = 0; k < 3; ++k) {
-            if (rvec) rvec[3 * (size_t)v + k] = x0[6 * (size_t)v + k];
-            if (tvec) tvec[3 * (size_t)v + k] = x0[6 * (size_t)v + 3 + k];
-        }
-        if (view_rms)
-            for (int c = 0; c < 2; ++c) view_rms[2 * (size_t)v + c] = std::sqrt(esq[2 * (size_t)v + c] / (double)(off[v + 1] - off[v]));
-    }
-    if (rms) *rms = std::sqrt(s.err / (2.0 * (double)corners));
-    if (iterations) *iterations = s.iter;
-    if (status) *status = s.status;
+    if (view_rms)
+        for (int v = 0; v < n; ++v)
+            for (int c = 0; c < 2; ++c)
+                view_rms[2 * (size_t)v + c] = std::sqrt(esq[2 * (size_t)v + c] / (double)(lp.off[v + 1] - lp.off[v]));
+    if (rms) *rms = std::sqrt(lp.s.err / (2.0 * (double)lp.corners));
+    if (iterations) *iterations = lp.s.iter;
+    if (status) *status = lp.s.status;
     return MCC_OK;
 }

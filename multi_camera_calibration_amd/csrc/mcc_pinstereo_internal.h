@@ -13,8 +13,8 @@ constexpr int kPsLinN = 702;          // PsLin::N  (mcc_pinstereo_device.hpp; as
 constexpr int kPsCtrN = 526;          // PsCtr::N
 constexpr int kPsYz = 186;            // Y_v [6][30], z_v [6]
 
-// The loop state is PcState (mcc_pincalib_internal.h): the policy is the same, and so are the writers
-// (k_ps_try's last arriver; `fail` by k_ps_lin's).
+// The loop state is PcState and the policy pc_next (mcc_pincalib_internal.h), shared through
+// mcc_pinloop_device.hpp; the writers are k_ps_try's last arriver and, of `fail`, k_ps_lin's.
 
 struct PsArgs {
     int n;                       // views
