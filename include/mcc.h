@@ -490,6 +490,112 @@ void mcc_pinrect_destroy(mcc_pinrect *h);
 int mcc_pinrect_remap(mcc_pinrect *h, const unsigned char *src, long long src_stride, unsigned char *dst,
                       long long dst_stride);
 
+/* ---- pinhole reconstruction: cv::reprojectImageTo3D, and a rectified pair to depth (stereoReconstruct for the
+ * K, D, R, T of mcc_stereo_calibrate).  DESIGN.md 7j states every rule and is the specification. */
+#define MCC_DISP_FLOAT 1     /* float pixels                                                             */
+#define MCC_DISP_FIXED16 2   /* short pixels, disparity x 16 as the matcher writes it                    */
+
+/* cv::reprojectImageTo3D: per pixel (x, y) with float disparity d, (X, Y, Z, W) = Q (x, y, (double)d, 1) in float64
+ * with the four terms of a row summed left to right and no fused multiply-add; points[(y width + x) 3 ..] =
+ * (float)(X / W), (float)(Y / W), (float)(Z / W).  W == 0 gives the IEEE inf or NaN, never a fault (a NaN
+ * is stored as the quiet NaN 0x7FC00000).  A MCC_DISP_FIXED16 pixel is
+ * converted as (float)d / 16.0f (exact) -- THIS DIFFERS FROM OpenCV, which takes a CV_16S disparity raw and leaves the
+ * division by 16 to the caller.  With handle_missing != 0 every pixel whose d is not above the minimum of the whole
+ * image gets Z = 10000.0f (OpenCV's bigZ), X and Y as above; a NaN disparity does not take part in the minimum.
+ * stride_bytes is the distance between rows, a multiple of the pixel size.  device_ms (may be NULL): the kernels alone,
+ * by HIP events.  MCC_EINVAL, before any device work, for a null pointer, a bad type, a size that is not positive or
+ * above 32767, or a stride shorter than a row or not a multiple of the pixel size. */
+int mcc_reproject_image_to_3d(const void *disparity, int disparity_type, int width, int height,
+                              long long stride_bytes, const double *Q /* [16] */, int handle_missing, int device,
+                              float *points /* [height*width*3] */, double *device_ms);
+
+/* the point types of include/mcc_omnidir.h (MCC_OMNI_XYZRGB, MCC_OMNI_XYZ) under model-neutral names */
+#define MCC_XYZRGB 1   /* 6 floats per point: x y z r g b */
+#define MCC_XYZ 2      /* 3 floats per point              */
+
+/* A rectified pinhole pair to depth, resident on the device for a stream of frame pairs.  create runs
+ * mcc_stereo_rectify on the host and builds both cameras' MCC_MAP_FIXED maps on the device; compute uploads the
+ * pair and runs the remap twice, the semi-global matcher of mcc_omnidir_sgbm (include/mcc_omnidir.h; d = x1 - x2 >= 0,
+ * no minDisparity, uniquenessRatio or speckle filter), the float disparity d16 / 16.0f (-1 where there is no match;
+ * a black pixel gets no special value), mcc_reproject_image_to_3d's kernel with Q and no missing-value handling,
+ * and the compacted cloud.
+ *
+ * The cloud: a pixel is a point iff d > 0, W is finite and not 0, Z / W > 0 (in float64), max_z <= 0 or
+ * Z / W <= max_z, and !use_roi or the pixel lies in roi1.  Points come in mcc_omnirecon's order (columns first, then
+ * rows), 3 or 6 floats each: the pixel's dense point, then for MCC_XYZRGB the three channels of rectified image 1 (a
+ * 1-channel value three times).
+ *
+ * Camera order: after rectification camera 2 must lie to the right of camera 1 (below it for a vertical pair), i.e.
+ * the component of R2 T along the baseline must be negative; otherwise create is MCC_EINVAL and says to swap.
+ *
+ * A vertical pair (mcc_stereo_rectify puts the baseline along y) is rectified into the TRANSPOSED frame: the
+ * rectified images are new_height wide and new_width high, so that the matcher sees a horizontal pair.  The maps
+ * are built from P1, P2 with rows 0 and 1 swapped, Q has columns 0 and 1 swapped, the rois are transposed, and every
+ * output (images, disparity, dense points, cloud order) is in that frame; mcc_pinrecon_info reports these. */
+typedef struct mcc_pinrecon mcc_pinrecon;
+
+typedef struct mcc_pinrecon_desc {
+    const double *K1, *D1, *K2, *D2;        /* [9], [nd] or NULL, as mcc_stereo_rectify          */
+    int nd;
+    const double *R, *T;                    /* [9], [3]                                          */
+    int src_width, src_height, channels;    /* both cameras; channels 1 or 3                     */
+    int rectify_flags;                      /* 0 or MCC_CALIB_ZERO_DISPARITY                     */
+    double alpha;                           /* as mcc_stereo_rectify                             */
+    int new_width, new_height;              /* 0: the source size                                */
+    int num_disparities, sad_window_size;   /* as mcc_omnidir_sgbm                               */
+    int point_type;                         /* MCC_XYZRGB or MCC_XYZ                             */
+    int use_roi;                            /* cloud only inside roi1                            */
+    double max_z;                           /* <= 0: no limit                                    */
+    int device;
+} mcc_pinrecon_desc;
+
+/* what the handle rectifies with, in the frame of its outputs (for a vertical pair the transposed one) */
+typedef struct mcc_pinrecon_geometry {
+    double R1[9], R2[9], P1[12], P2[12], Q[16];
+    int roi1[4], roi2[4];                   /* x, y, width, height                               */
+    int width, height;                      /* of the rectified images, the disparity and points */
+    int transposed;                         /* 1 for a vertical pair                             */
+} mcc_pinrecon_geometry;
+
+/* MCC_EINVAL with a message, before any device work, for everything mcc_stereo_rectify and mcc_omnidir_sgbm refuse
+ * (sizes, channels, num_disparities not a multiple of 16 or above 256 or not below the matched width, an even
+ * window, 93 channels window^2 > 32767, a cost volume above MCC_OMNI_SGBM_MAX_COST_BYTES), nd = 14, a bad point type
+ * and the camera order. */
+int mcc_pinrecon_create(mcc_pinrecon **out, const mcc_pinrecon_desc *desc);
+void mcc_pinrecon_destroy(mcc_pinrecon *h);
+int mcc_pinrecon_info(const mcc_pinrecon *h, mcc_pinrecon_geometry *geometry);
+
+/* One pair.  Out: disparity (float [height*width]), rec1, rec2 (the rectified images, strides in bytes); disparity16
+ * (the matcher's short [height*width], -16 where there is no match), points (float [height*width*3]) and cloud may
+ * be NULL (cloud only with capacity 0).  capacity counts points; *n_points is the number of points of the cloud.  If
+ * it exceeds capacity the call is MCC_EINVAL, *n_points still holds it and cloud is untouched. */
+int mcc_pinrecon_compute(mcc_pinrecon *h, const unsigned char *image1, long long stride1,
+                         const unsigned char *image2, long long stride2, float *disparity, short *disparity16,
+                         unsigned char *rec1, long long rec1_stride, unsigned char *rec2, long long rec2_stride,
+                         float *points, float *cloud, long long capacity, long long *n_points);
+
+/* device milliseconds per pair over n_frames back-to-back computes (every kernel, no transfer) on resident random
+ * frames, by HIP events */
+int mcc_pinrecon_time(mcc_pinrecon *h, int n_frames, double *ms_per_frame);
+
+/* A handle used once.  Both images' sizes and channel counts are given so that a mismatch, between them or with
+ * desc, is refused; geometry (may be NULL) is filled before the pair is computed, so that a caller can size its
+ * outputs from a first call that fails for a too small capacity. */
+int mcc_stereo_reconstruct(const unsigned char *image1, int width, int height, int channels, long long stride1,
+                           const unsigned char *image2, int width2, int height2, int channels2, long long stride2,
+                           const mcc_pinrecon_desc *desc, mcc_pinrecon_geometry *geometry, float *disparity,
+                           short *disparity16, unsigned char *rec1, long long rec1_stride, unsigned char *rec2,
+                           long long rec2_stride, float *points, float *cloud, long long capacity,
+                           long long *n_points);
+
+/* The cloud rule on the host, through the very function the count and the write kernel compile: the cloud of a float
+ * disparity [height*width] under Q, with the dense points computed as mcc_reproject_image_to_3d does.  rec1 (packed
+ * rows, may be NULL with MCC_XYZ) gives the colours, roi (may be NULL: no roi) is x, y, width, height.  Capacity as
+ * mcc_pinrecon_compute.  No device call. */
+int mcc_pinrecon_host_cloud(const float *disparity, int width, int height, const double *Q,
+                            const unsigned char *rec1, int channels, int point_type, const int *roi, double max_z,
+                            float *cloud, long long capacity, long long *n_points);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,8 @@
  *
  * cv::stereoCalibrate for a pinhole pair is further down, over mcc_stereo_calibrate, and after it
  * the rectification of what the two return: undistortPoints, initUndistortRectifyMap, undistort, stereoRectify
- * (DESIGN.md 7i).
+ * (DESIGN.md 7i), and the reconstruction from a rectified pair: reprojectImageTo3D, stereoReconstruct and the
+ * Reconstructor for streams of pairs.
  */
 #ifndef MCC_CALIB_HPP
 #define MCC_CALIB_HPP
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "mcc.h"
+#include "mcc_cvmat.hpp"
 #include "mcc_multicalib.hpp"
 
 namespace mcc {
@@ -169,6 +171,77 @@ void stereoRectify(const std::array<double, 9>& cameraMatrix1, const std::vector
                    std::array<double, 12>& P1, std::array<double, 12>& P2, std::array<double, 16>& Q,
                    int flags = CALIB_ZERO_DISPARITY, double alpha = -1, Size newImageSize = Size(),
                    Rect* validPixROI1 = nullptr, Rect* validPixROI2 = nullptr);
+
+/*
+ * Reconstruction over mcc_reproject_image_to_3d and mcc_pinrecon_*, on the project's cv::Mat
+ * (mcc_cvmat.hpp):
+ *
+ *   void reprojectImageTo3D(InputArray disparity, OutputArray _3dImage, InputArray Q, bool handleMissingValues = false);
+ *
+ * disparity is CV_32F (the project's cv::Mat has no 16-bit type; the C ABI and Python take the matcher's fixed-point
+ * disparity too), Q is 4 x 4 CV_32F or CV_64F, _3dImage comes back CV_32FC3.  stereoReconstruct is the pinhole
+ * counterpart of mcc::omnidir::stereoReconstruct: 8-bit images of 1 or 3 channels in; the float disparity (CV_32F),
+ * both rectified images, the dense points (CV_32FC3, optional) and the cloud (N x 1, CV_32FC3 for XYZ, CV_32FC(6) for
+ * XYZRGB) out.  Camera 2 must lie to the right of camera 1 after rectification, or below it: such a vertical pair
+ * comes out in the transposed frame (ReconstructInfo::transposed, 7j).  Wrong sizes and types throw
+ * std::invalid_argument, whatever the C ABI refuses std::runtime_error with the library's message.
+ */
+enum { XYZRGB = MCC_XYZRGB, XYZ = MCC_XYZ };
+
+void reprojectImageTo3D(const cv::Mat& disparity, cv::Mat& _3dImage, const cv::Mat& Q, bool handleMissingValues = false,
+                        int device = 0);
+
+// what the pair is rectified with, in the frame of the outputs (mcc_pinrecon_geometry)
+struct ReconstructInfo {
+    std::array<double, 9> R1{}, R2{};
+    std::array<double, 12> P1{}, P2{};
+    std::array<double, 16> Q{};
+    Rect roi1, roi2;
+    Size size;
+    bool transposed = false;
+};
+
+struct ReconstructOptions {
+    int flags = CALIB_ZERO_DISPARITY;   // stereoRectify's
+    double alpha = -1;
+    Size newImageSize = Size();         // empty: the source size
+    int pointType = XYZRGB;
+    bool useRoi = false;                // cloud only inside roi1
+    double maxZ = 0;                    // <= 0: no limit
+    int device = 0;
+};
+
+// A stream of pairs: stereoRectify's result, both cameras' maps and every buffer stay on the device (mcc_pinrecon).
+class Reconstructor {
+public:
+    Reconstructor(const std::array<double, 9>& cameraMatrix1, const std::vector<double>& distCoeffs1,
+                  const std::array<double, 9>& cameraMatrix2, const std::vector<double>& distCoeffs2, Size imageSize,
+                  int channels, const std::array<double, 9>& R, const Vec3d& T, int numDisparities, int SADWindowSize,
+                  const ReconstructOptions& options = ReconstructOptions());
+    ~Reconstructor();
+    Reconstructor(const Reconstructor&) = delete;
+    Reconstructor& operator=(const Reconstructor&) = delete;
+
+    // points3d (may be null) gets the dense CV_32FC3 points
+    void compute(const cv::Mat& image1, const cv::Mat& image2, cv::Mat& disparity, cv::Mat& image1Rec, cv::Mat& image2Rec,
+                 cv::Mat& pointCloud, cv::Mat* points3d = nullptr);
+    double time(int frames);   // device milliseconds per pair, no transfers
+    const ReconstructInfo& info() const { return info_; }
+
+private:
+    mcc_pinrecon* h_ = nullptr;
+    ReconstructInfo info_;
+    Size src_;
+    int channels_ = 1, point_floats_ = 6;
+};
+
+// one Reconstructor used once
+void stereoReconstruct(const cv::Mat& image1, const cv::Mat& image2, const std::array<double, 9>& cameraMatrix1,
+                       const std::vector<double>& distCoeffs1, const std::array<double, 9>& cameraMatrix2,
+                       const std::vector<double>& distCoeffs2, const std::array<double, 9>& R, const Vec3d& T,
+                       int numDisparities, int SADWindowSize, cv::Mat& disparity, cv::Mat& image1Rec, cv::Mat& image2Rec,
+                       cv::Mat& pointCloud, const ReconstructOptions& options = ReconstructOptions(),
+                       cv::Mat* points3d = nullptr, ReconstructInfo* info = nullptr);
 
 }  // namespace calib
 }  // namespace mcc

@@ -113,6 +113,24 @@ class _PinRectDesc(ctypes.Structure):
                 ("src_height", ctypes.c_int), ("channels", ctypes.c_int), ("device", ctypes.c_int)]
 
 
+class _PinReconDesc(ctypes.Structure):
+    _fields_ = [("K1", _f64p), ("D1", _f64p), ("K2", _f64p), ("D2", _f64p), ("nd", ctypes.c_int), ("R", _f64p),
+                ("T", _f64p), ("src_width", ctypes.c_int), ("src_height", ctypes.c_int), ("channels", ctypes.c_int),
+                ("rectify_flags", ctypes.c_int), ("alpha", ctypes.c_double), ("new_width", ctypes.c_int),
+                ("new_height", ctypes.c_int), ("num_disparities", ctypes.c_int), ("sad_window_size", ctypes.c_int),
+                ("point_type", ctypes.c_int), ("use_roi", ctypes.c_int), ("max_z", ctypes.c_double),
+                ("device", ctypes.c_int)]
+
+
+class _PinReconGeometry(ctypes.Structure):
+    _fields_ = [("R1", ctypes.c_double * 9), ("R2", ctypes.c_double * 9), ("P1", ctypes.c_double * 12),
+                ("P2", ctypes.c_double * 12), ("Q", ctypes.c_double * 16), ("roi1", ctypes.c_int * 4),
+                ("roi2", ctypes.c_int * 4), ("width", ctypes.c_int), ("height", ctypes.c_int),
+                ("transposed", ctypes.c_int)]
+
+
+DISP_FLOAT, DISP_FIXED16 = 1, 2   # include/mcc.h: MCC_DISP_*
+
 _LIB = None
 
 
@@ -269,10 +287,23 @@ def lib():
                                          _f64p, _f64p] + [ctypes.c_int] * 4 + [_u8p, _ll]),
                 ("mcc_pinrect_create", [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_PinRectDesc)]),
                 ("mcc_pinrect_destroy", [ctypes.c_void_p]),
-                ("mcc_pinrect_remap", [ctypes.c_void_p, _u8p, _ll, _u8p, _ll])):
+                ("mcc_pinrect_remap", [ctypes.c_void_p, _u8p, _ll, _u8p, _ll]),
+                ("mcc_reproject_image_to_3d", [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ll, _f64p,
+                                               ctypes.c_int, ctypes.c_int, _f32p, _f64p]),
+                ("mcc_pinrecon_create", [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_PinReconDesc)]),
+                ("mcc_pinrecon_destroy", [ctypes.c_void_p]),
+                ("mcc_pinrecon_info", [ctypes.c_void_p, ctypes.POINTER(_PinReconGeometry)]),
+                ("mcc_pinrecon_compute", [ctypes.c_void_p, _u8p, _ll, _u8p, _ll, _f32p, _i16p, _u8p, _ll, _u8p, _ll, _f32p,
+                                          _f32p, _ll, ctypes.POINTER(_ll)]),
+                ("mcc_pinrecon_time", [ctypes.c_void_p, ctypes.c_int, _f64p]),
+                ("mcc_stereo_reconstruct", [_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ll] * 2 +
+                 [ctypes.POINTER(_PinReconDesc), ctypes.POINTER(_PinReconGeometry), _f32p, _i16p, _u8p, _ll, _u8p, _ll,
+                  _f32p, _f32p, _ll, ctypes.POINTER(_ll)]),
+                ("mcc_pinrecon_host_cloud", [_f32p, ctypes.c_int, ctypes.c_int, _f64p, _u8p, ctypes.c_int, ctypes.c_int,
+                                             _i32p, ctypes.c_double, _f32p, _ll, ctypes.POINTER(_ll)])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
-        for name in ("mcc_omnirect_destroy", "mcc_omnirecon_destroy", "mcc_pinrect_destroy"):
+        for name in ("mcc_omnirect_destroy", "mcc_omnirecon_destroy", "mcc_pinrect_destroy", "mcc_pinrecon_destroy"):
             if hasattr(L, name):
                 getattr(L, name).restype = None
         _LIB = L
@@ -1357,3 +1388,170 @@ def omnidir_stereo_reconstruct(image1, image2, K1, D1, xi1, K2, D2, xi2, R, T, f
         return rec.compute(image1, image2, capacity)
     finally:
         rec.close()
+
+
+# ---------------------------------------------------------------- pinhole reconstruction
+# include/mcc.h: cv::reprojectImageTo3D and a rectified pinhole pair to depth, for the K, D, R, T of stereo_calibrate.
+def reproject_image_to_3d(disparity, Q, handle_missing=False, device=0, return_ms=False):
+    """cv::reprojectImageTo3D (mcc_reproject_image_to_3d): float32 [h, w, 3] = Q (x, y, d, 1) dehomogenised, per pixel
+    of a float32 disparity [h, w] or of an int16 one, which holds disparity x 16 as the matcher writes it and is
+    divided by 16 here (OpenCV takes a CV_16S disparity raw).  Rows may be strided.  With handle_missing every pixel
+    at the image's minimum gets Z = 10000."""
+    d = disparity
+    if not isinstance(d, np.ndarray) or d.ndim != 2 or d.dtype not in (np.float32, np.int16):
+        raise MccError("disparity must be a float32 or int16 array [h, w]")
+    if d.strides[1] != d.itemsize or d.strides[0] < 0:
+        d = np.ascontiguousarray(d)
+    h, w = d.shape
+    Q = np.ascontiguousarray(Q, np.float64)
+    if Q.shape != (4, 4):
+        raise MccError("Q must be 4 x 4")
+    out, ms = np.zeros((max(h, 0), max(w, 0), 3), np.float32), np.zeros(1)
+    _check(lib().mcc_reproject_image_to_3d(d.ctypes.data_as(ctypes.c_void_p), DISP_FLOAT if d.dtype == np.float32 else DISP_FIXED16,
+                                           w, h, d.strides[0], _ptr(Q, _f64p), int(bool(handle_missing)), device,
+                                           _ptr(out, _f32p), _ptr(ms, _f64p)), "mcc_reproject_image_to_3d")
+    return (out, float(ms[0])) if return_ms else out
+
+
+def _geometry(g):
+    """mcc_pinrecon_geometry as a dict of arrays"""
+    return dict(R1=np.array(g.R1).reshape(3, 3), R2=np.array(g.R2).reshape(3, 3), P1=np.array(g.P1).reshape(3, 4),
+                P2=np.array(g.P2).reshape(3, 4), Q=np.array(g.Q).reshape(4, 4), roi1=tuple(g.roi1), roi2=tuple(g.roi2),
+                size=(g.width, g.height), transposed=bool(g.transposed))
+
+
+def pinhole_cloud_host(disparity, Q, rec1=None, point_type=XYZ, roi=None, max_z=0.0):
+    """The cloud rule of 7j on the host (mcc_pinrecon_host_cloud; no GPU), through the function the device's count and
+    write kernels compile: float32 [n, 3 or 6] of a float32 disparity [h, w]."""
+    d = np.ascontiguousarray(disparity, np.float32)
+    h, w = d.shape
+    Q = np.ascontiguousarray(Q, np.float64).reshape(4, 4)
+    c = 1
+    if rec1 is not None:
+        rec1, rw, rh, c, _ = _image(np.ascontiguousarray(rec1), "rec1")
+        if (rw, rh) != (w, h):
+            raise MccError("rec1 must have the disparity's size")
+    roi = None if roi is None else np.ascontiguousarray(roi, np.int32)
+    nf = 3 if point_type == XYZ else 6
+    cloud = np.zeros((w * h, nf), np.float32)
+    n = ctypes.c_longlong(0)
+    _check(lib().mcc_pinrecon_host_cloud(_ptr(d, _f32p), w, h, _ptr(Q, _f64p), _ptr(rec1, _u8p), c, int(point_type),
+                                         _ptr(roi, _i32p), float(max_z), _ptr(cloud, _f32p), w * h, ctypes.byref(n)),
+           "mcc_pinrecon_host_cloud")
+    return cloud[:n.value].copy()
+
+
+def _pinrecon_desc(K1, D1, K2, D2, R, T, num_disparities, sad_window_size, src_size, channels, flags, alpha, new_size,
+                   point_type, use_roi, max_z, device):
+    """(mcc_pinrecon_desc, the arrays it points into)"""
+    (D1, nd), (D2, nd2) = _dist(D1), _dist(D2)
+    if D1 is not None and D2 is not None and nd != nd2:
+        raise MccError("D1 and D2 must hold the same number of coefficients")
+    keep = [_mat3(K1, "K1"), D1, _mat3(K2, "K2"), D2, _mat3(R, "R", True), _vec(T, 3, "T")]
+    d = _PinReconDesc()
+    d.K1, d.D1, d.K2, d.D2, d.R, d.T = (_ptr(a, _f64p) for a in keep)
+    d.nd, d.device = max(nd, nd2), int(device)
+    d.src_width, d.src_height = int(src_size[0]), int(src_size[1])
+    d.channels, d.point_type = int(channels), int(point_type)
+    d.rectify_flags, d.alpha = int(flags), float(alpha)
+    d.new_width, d.new_height = (0, 0) if new_size is None else (int(new_size[0]), int(new_size[1]))
+    d.num_disparities, d.sad_window_size = int(num_disparities), int(sad_window_size)
+    d.use_roi, d.max_z = int(bool(use_roi)), float(max_z)
+    return d, keep
+
+
+class _PinReconOutputs:
+    """the host buffers of one compute for outputs of out_size = (width, height)"""
+
+    def __init__(self, out_size, channels, point_type, squeeze, capacity, dense):
+        w, h = out_size
+        self.cap = w * h if capacity is None else int(capacity)
+        self.disp, self.disp16 = np.zeros((h, w), np.float32), np.zeros((h, w), np.int16)
+        (self.rec1, self.rs1), (self.rec2, self.rs2) = (_dst_image(None, w, h, channels, squeeze) for _ in range(2))
+        self.points = np.zeros((h, w, 3), np.float32) if dense else None
+        self.cloud = np.zeros((max(self.cap, 0), 3 if point_type == XYZ else 6), np.float32)
+        self.n = ctypes.c_longlong(0)
+
+    def args(self):
+        return [_ptr(self.disp, _f32p), _ptr(self.disp16, _i16p), _ptr(self.rec1, _u8p), self.rs1, _ptr(self.rec2, _u8p),
+                self.rs2, _ptr(self.points, _f32p), _ptr(self.cloud, _f32p) if self.cap > 0 else None, self.cap,
+                ctypes.byref(self.n)]
+
+    def result(self, **extra):
+        return dict(disparity=self.disp, disparity16=self.disp16, rec1=self.rec1, rec2=self.rec2, points=self.points,
+                    cloud=self.cloud[:self.n.value].copy(), **extra)
+
+
+class PinholeReconstructor:
+    """The per-pair case of stereo_reconstruct (mcc_pinrecon): stereo_rectify's result, both cameras' fixed-point maps,
+    the images, the matcher's volumes, the dense points and the cloud stay on the device for a stream of frame pairs.
+
+    Camera 2 must lie to the right of camera 1 after rectification (below it for a vertical pair).  A vertical pair
+    comes out in the transposed frame: info()["transposed"], and every output has info()["size"] = (width, height)."""
+
+    def __init__(self, K1, D1, K2, D2, R, T, num_disparities, sad_window_size, src_size, channels=1,
+                 flags=CV_CALIB_ZERO_DISPARITY, alpha=-1.0, new_size=None, point_type=XYZRGB, use_roi=False, max_z=0.0,
+                 device=0):
+        d, self._keep = _pinrecon_desc(K1, D1, K2, D2, R, T, num_disparities, sad_window_size, src_size, channels, flags,
+                                       alpha, new_size, point_type, use_roi, max_z, device)
+        self.src_size, self.channels, self.point_type = (d.src_width, d.src_height), d.channels, d.point_type
+        h = ctypes.c_void_p()
+        _check(lib().mcc_pinrecon_create(ctypes.byref(h), ctypes.byref(d)), "mcc_pinrecon_create")
+        self.h = h
+        g = _PinReconGeometry()
+        _check(lib().mcc_pinrecon_info(self.h, ctypes.byref(g)), "mcc_pinrecon_info")
+        self._info = _geometry(g)
+        self.out_size = self._info["size"]
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcc_pinrecon_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """R1 R2 P1 P2 Q roi1 roi2 in the frame of the outputs, their size (width, height) and `transposed`."""
+        return dict(self._info)
+
+    def compute(self, image1, image2, capacity=None, dense=True):
+        """One frame pair -> dict(disparity float32 [h, w], disparity16 int16 [h, w] (x 16, -16: no match), rec1, rec2,
+        points float32 [h, w, 3] (None without dense), cloud float32 [n, 3 or 6]).  capacity bounds the number of points
+        (default: every pixel); too small a one raises MccError."""
+        image1, w1, h1, c1, s1 = _image(image1, "image1")
+        image2, w2, h2, c2, s2 = _image(image2, "image2")
+        if (w1, h1) != self.src_size or (w2, h2) != self.src_size or c1 != self.channels or c2 != self.channels:
+            raise MccError(f"both images must be {self.src_size[1]} x {self.src_size[0]} x {self.channels}")
+        o = _PinReconOutputs(self.out_size, self.channels, self.point_type, image1.ndim == 2, capacity, dense)
+        _check(lib().mcc_pinrecon_compute(self.h, _ptr(image1, _u8p), s1, _ptr(image2, _u8p), s2, *o.args()),
+               "mcc_pinrecon_compute")
+        return o.result()
+
+    def time(self, n_frames):
+        """Device milliseconds per frame pair over n_frames back-to-back computes on resident random frames."""
+        ms = ctypes.c_double(0)
+        _check(lib().mcc_pinrecon_time(self.h, int(n_frames), ctypes.byref(ms)), "mcc_pinrecon_time")
+        return ms.value
+
+
+def stereo_reconstruct(image1, image2, K1, D1, K2, D2, R, T, num_disparities, sad_window_size,
+                       flags=CV_CALIB_ZERO_DISPARITY, alpha=-1.0, new_size=None, point_type=XYZRGB, use_roi=False, max_z=0.0,
+                       capacity=None, dense=True, device=0):
+    """A rectified pair to depth in one call (mcc_stereo_reconstruct, a handle used once): PinholeReconstructor.compute's
+    dict plus "info".  The arguments are PinholeReconstructor's."""
+    image1, w, h, c, s1 = _image(image1, "image1")
+    image2, w2, h2, c2, s2 = _image(image2, "image2")
+    d, keep = _pinrecon_desc(K1, D1, K2, D2, R, T, num_disparities, sad_window_size, (w, h), c, flags, alpha, new_size,
+                             point_type, use_roi, max_z, device)
+    # the size of the outputs: the new size, transposed for a vertical pair (stereo_rectify is host code)
+    P2 = stereo_rectify(keep[0], keep[1], keep[2], keep[3], (w, h), keep[4], keep[5], flags, alpha, new_size)[3]
+    W, H = (w, h) if new_size is None else (d.new_width, d.new_height)
+    o = _PinReconOutputs((W, H) if P2[0, 3] != 0 else (H, W), c, d.point_type, image1.ndim == 2, capacity, dense)
+    g = _PinReconGeometry()
+    _check(lib().mcc_stereo_reconstruct(_ptr(image1, _u8p), w, h, c, s1, _ptr(image2, _u8p), w2, h2, c2, s2, ctypes.byref(d),
+                                        ctypes.byref(g), *o.args()), "mcc_stereo_reconstruct")
+    return o.result(info=_geometry(g))

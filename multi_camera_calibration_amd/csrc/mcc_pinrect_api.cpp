@@ -149,6 +149,11 @@ void pr_rectangles(const mcc::PnpCam& cam, const double* R, const double* Kn, in
 
 }  // namespace
 
+int mcc_pr_map_args(const double* K, const double* D, int nd, const double* R, const double* P, int ld, int w, int h,
+                    mcc::PrMapArgs* a, bool* rational) {
+    return pr_map_args(K, D, nd, R, P, ld, w, h, a, rational);
+}
+
 extern "C" {
 
 int mcc_undistort_points(int n, const double* src, const double* K, const double* D, int nd, const double* R,

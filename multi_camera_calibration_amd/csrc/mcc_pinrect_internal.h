@@ -63,3 +63,7 @@ struct PrPointsArgs {
 // map_type: MCC_MAP_*; rational: any of k4 k5 k6 is not 0 (both checked by the callers)
 hipError_t mcc_launch_pr_map(const mcc::PrMapArgs& a, int map_type, bool rational, hipStream_t s);
 hipError_t mcc_launch_pr_points(const mcc::PrPointsArgs& a, hipStream_t s);
+// the host part of mcc_init_undistort_rectify_map (mcc_pinrect_api.cpp): the argument checks and (P R)^-1, everything
+// k_pr_map takes but the maps; MCC_OK or MCC_EINVAL with the message set.  mcc_pinrecon_api.cpp builds its maps with it.
+int mcc_pr_map_args(const double* K, const double* D, int nd, const double* R, const double* P, int ld, int w, int h,
+                    mcc::PrMapArgs* a, bool* rational);

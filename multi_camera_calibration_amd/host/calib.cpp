@@ -2,10 +2,13 @@
 // argument order over mcc_calibrate_camera / mcc_init_camera_matrix (reference call sites
 // src/multicalib.cpp:254-256, samples/random_pattern_calibration.cpp:159, src/ccalib.cpp:423), stereoCalibrate over
 // mcc_stereo_calibrate, and the rectification calls undistortPoints, initUndistortRectifyMap, undistort and stereoRectify
-// over mcc_undistort_points, mcc_init_undistort_rectify_map, mcc_undistort_image and mcc_stereo_rectify.
+// over mcc_undistort_points, mcc_init_undistort_rectify_map, mcc_undistort_image and mcc_stereo_rectify, and the
+// reconstruction calls reprojectImageTo3D, Reconstructor and stereoReconstruct over mcc_reproject_image_to_3d and
+// mcc_pinrecon_*.
 #include "mcc_calib.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 
@@ -242,6 +245,112 @@ void stereoRectify(const std::array<double, 9>& cameraMatrix1, const std::vector
     Rect* out[2] = {validPixROI1, validPixROI2};
     for (int k = 0; k < 2; ++k)
         if (out[k]) *out[k] = Rect{roi[k][0], roi[k][1], roi[k][2], roi[k][3]};
+}
+
+// ---------------------------------------------------------------- reconstruction
+void reprojectImageTo3D(const cv::Mat& disparity, cv::Mat& _3dImage, const cv::Mat& Q, bool handleMissingValues, int device) {
+    const char* who = "reprojectImageTo3D";
+    if (disparity.empty() || disparity.type() != CV_32FC1)
+        throw std::invalid_argument(std::string(who) + ": disparity must be CV_32FC1 and not empty");
+    if (Q.rows != 4 || Q.cols != 4 || Q.channels() != 1 || (Q.depth() != CV_32F && Q.depth() != CV_64F))
+        throw std::invalid_argument(std::string(who) + ": Q must be 4 x 4, CV_32F or CV_64F");
+    double q[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) q[4 * r + c] = Q.scalar(r, c);
+    _3dImage.create(disparity.rows, disparity.cols, CV_32FC3);
+    const int rc = mcc_reproject_image_to_3d(disparity.data, MCC_DISP_FLOAT, disparity.cols, disparity.rows,
+                                             (long long)disparity.step(), q, handleMissingValues ? 1 : 0, device,
+                                             _3dImage.ptr<float>(), nullptr);
+    if (rc != MCC_OK) throw std::runtime_error(std::string(who) + ": " + mcc_last_error());
+}
+
+namespace {
+
+ReconstructInfo info_of(const mcc_pinrecon_geometry& g) {
+    ReconstructInfo i;
+    std::copy(g.R1, g.R1 + 9, i.R1.begin());
+    std::copy(g.R2, g.R2 + 9, i.R2.begin());
+    std::copy(g.P1, g.P1 + 12, i.P1.begin());
+    std::copy(g.P2, g.P2 + 12, i.P2.begin());
+    std::copy(g.Q, g.Q + 16, i.Q.begin());
+    i.roi1 = Rect{g.roi1[0], g.roi1[1], g.roi1[2], g.roi1[3]};
+    i.roi2 = Rect{g.roi2[0], g.roi2[1], g.roi2[2], g.roi2[3]};
+    i.size = Size(g.width, g.height);
+    i.transposed = g.transposed != 0;
+    return i;
+}
+
+void check_image(const cv::Mat& im, Size size, int channels, const char* who) {
+    if (im.empty() || im.depth() != CV_8U || im.channels() != channels || im.cols != size.width || im.rows != size.height)
+        throw std::invalid_argument(std::string(who) + ": the images must be CV_8U of " + std::to_string(size.width) + " x " +
+                                    std::to_string(size.height) + " with " + std::to_string(channels) + " channel(s)");
+}
+
+}  // namespace
+
+Reconstructor::Reconstructor(const std::array<double, 9>& cameraMatrix1, const std::vector<double>& distCoeffs1,
+                             const std::array<double, 9>& cameraMatrix2, const std::vector<double>& distCoeffs2, Size imageSize,
+                             int channels, const std::array<double, 9>& R, const Vec3d& T, int numDisparities,
+                             int SADWindowSize, const ReconstructOptions& o)
+    : src_(imageSize), channels_(channels), point_floats_(o.pointType == XYZ ? 3 : 6) {
+    // one nd for both cameras: the shorter vector is padded with zeros
+    const size_t nd = std::max(distCoeffs1.size(), distCoeffs2.size());
+    std::vector<double> d1(distCoeffs1), d2(distCoeffs2);
+    d1.resize(nd, 0.0);
+    d2.resize(nd, 0.0);
+    const mcc_pinrecon_desc d{cameraMatrix1.data(), nd ? d1.data() : nullptr, cameraMatrix2.data(), nd ? d2.data() : nullptr,
+                              (int)nd, R.data(), T.data(), imageSize.width, imageSize.height, channels, o.flags, o.alpha,
+                              o.newImageSize.width, o.newImageSize.height, numDisparities, SADWindowSize, o.pointType,
+                              o.useRoi ? 1 : 0, o.maxZ, o.device};
+    if (mcc_pinrecon_create(&h_, &d) != MCC_OK) throw std::runtime_error(std::string("Reconstructor: ") + mcc_last_error());
+    mcc_pinrecon_geometry g;
+    mcc_pinrecon_info(h_, &g);
+    info_ = info_of(g);
+}
+
+Reconstructor::~Reconstructor() { mcc_pinrecon_destroy(h_); }
+
+void Reconstructor::compute(const cv::Mat& image1, const cv::Mat& image2, cv::Mat& disparity, cv::Mat& image1Rec,
+                            cv::Mat& image2Rec, cv::Mat& pointCloud, cv::Mat* points3d) {
+    const char* who = "Reconstructor::compute";
+    check_image(image1, src_, channels_, who);
+    check_image(image2, src_, channels_, who);
+    const int w = info_.size.width, h = info_.size.height;
+    disparity.create(h, w, CV_32F);
+    image1Rec.create(h, w, image1.type());
+    image2Rec.create(h, w, image1.type());
+    if (points3d) points3d->create(h, w, CV_32FC3);
+    std::vector<float> pts((size_t)w * h * point_floats_);
+    long long n = 0;
+    const int rc = mcc_pinrecon_compute(h_, image1.data, (long long)image1.step(), image2.data, (long long)image2.step(),
+                                        disparity.ptr<float>(), nullptr, image1Rec.data, (long long)image1Rec.step(),
+                                        image2Rec.data, (long long)image2Rec.step(), points3d ? points3d->ptr<float>() : nullptr,
+                                        pts.data(), (long long)w * h, &n);
+    if (rc != MCC_OK) throw std::runtime_error(std::string(who) + ": " + mcc_last_error());
+    pointCloud.create((int)n, 1, CV_32FC(point_floats_));
+    if (n > 0) std::memcpy(pointCloud.data, pts.data(), sizeof(float) * (size_t)n * point_floats_);
+}
+
+double Reconstructor::time(int frames) {
+    double ms = 0;
+    if (mcc_pinrecon_time(h_, frames, &ms) != MCC_OK) throw std::runtime_error(std::string("Reconstructor::time: ") + mcc_last_error());
+    return ms;
+}
+
+void stereoReconstruct(const cv::Mat& image1, const cv::Mat& image2, const std::array<double, 9>& cameraMatrix1,
+                       const std::vector<double>& distCoeffs1, const std::array<double, 9>& cameraMatrix2,
+                       const std::vector<double>& distCoeffs2, const std::array<double, 9>& R, const Vec3d& T,
+                       int numDisparities, int SADWindowSize, cv::Mat& disparity, cv::Mat& image1Rec, cv::Mat& image2Rec,
+                       cv::Mat& pointCloud, const ReconstructOptions& options, cv::Mat* points3d, ReconstructInfo* info) {
+    const char* who = "stereoReconstruct";
+    if (image1.empty() || image1.depth() != CV_8U || (image1.channels() != 1 && image1.channels() != 3))
+        throw std::invalid_argument(std::string(who) + ": the images must be CV_8UC1 or CV_8UC3 and not empty");
+    const Size size(image1.cols, image1.rows);
+    check_image(image2, size, image1.channels(), who);
+    Reconstructor rec(cameraMatrix1, distCoeffs1, cameraMatrix2, distCoeffs2, size, image1.channels(), R, T, numDisparities,
+                      SADWindowSize, options);
+    if (info) *info = rec.info();
+    rec.compute(image1, image2, disparity, image1Rec, image2Rec, pointCloud, points3d);
 }
 
 }  // namespace calib
