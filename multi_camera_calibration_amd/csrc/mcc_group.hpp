@@ -819,14 +819,23 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
     int q0 = first_lane(hdr[kGHdrRange + 4]), nq = first_lane(hdr[kGHdrRange + 5]);
     int c0 = first_lane(hdr[kGHdrRange + 6]), nc = first_lane(hdr[kGHdrRange + 7]);
     GroupHot hp = kernarg_at<GroupHot>(kGArgHot);
+    // what the photo phase reads of LinArgs, in the same batch: between the rounds and the slot stores
+    // nothing waits for an argument (each read there stood behind a wait of its own, two of them between
+    // the Cholesky's LDS stores and the barrier that the other seven waves stand at)
+    const LinArgs& a = kernarg_at<LinArgs>(kGArgLin);
+    double* fnorm = a.fnorm;
+    double* pairprod = a.pairprod;
+    int fault_photo = a.fault_photo;
     // (every value in a register at one point: the loads are issued together ahead of it)
     asm volatile("" ::"s"(done), "s"(pending), "s"(alpha_prev), "s"(p0), "s"(np), "s"(ge0), "s"(gne), "s"(q0), "s"(nq),
                  "s"(c0), "s"(nc), "s"(hp.gpairs), "s"(hp.gcon), "s"(hp.dg), "s"(hp.kintr), "s"(hp.x), "s"(hp.cam_rt),
                  "s"(hp.ds_rt), "s"(hp.zp), "s"(hp.photo_norm), "s"(hp.gblock), "s"(hp.Y), "s"(hp.obj_x), "s"(hp.obj_y),
                  "s"(hp.obj_z), "s"(hp.img_u), "s"(hp.img_v), "s"(hp.stamps), "s"(hp.global_dim), "s"(hp.n_cams));
-    asm volatile("" ::"s"(hp.edge_info), "s"(hp.edge_lphoto), "s"(hp.gp_tot), "s"(hp.resid));
+    asm volatile("" ::"s"(hp.edge_info), "s"(hp.edge_lphoto), "s"(hp.gp_tot), "s"(hp.resid), "s"(fnorm), "s"(pairprod),
+                 "s"(fault_photo));
     asm volatile("" : "+s"(done), "+s"(pending), "+s"(alpha_prev), "+s"(p0), "+s"(np), "+s"(ge0), "+s"(gne), "+s"(q0),
-                 "+s"(nq), "+s"(c0), "+s"(nc), "+s"(hp.global_dim), "+s"(hp.n_cams));
+                 "+s"(nq), "+s"(c0), "+s"(nc), "+s"(hp.global_dim), "+s"(hp.n_cams), "+s"(fault_photo));
+    fnorm = pin_global(fnorm); pairprod = pin_global(pairprod);
     // (pinned as global-memory pointers: a generic pointer out of an asm statement makes its loads flat ones)
     hp.gpairs = pin_global(hp.gpairs); hp.gcon = pin_global(hp.gcon); hp.dg = pin_global(hp.dg);
     hp.kintr = pin_global(hp.kintr); hp.x = pin_global(hp.x); hp.cam_rt = pin_global(hp.cam_rt);
@@ -1030,8 +1039,6 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
     for (int t = NT + tid; t < kGIntr * C; t += NT) ktab[t] = hp.kintr[t];
     __syncthreads();
     SSTAMP(stp, 1, 0);
-    // what the later phases read of the other arguments: from here on (no scalar wait inside the batch above)
-    const LinArgs& a = kernarg_at<LinArgs>(kGArgLin);
     if (pending) {
         for (int t = tid; t < 6 * gne; t += NT) {
             const int le = t / 6, k = t % 6;
@@ -1255,8 +1262,26 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
     SSTAMP(stp, 6, 0);
 
     // ---- phase B: k_photo's photo work on the group's LDS records
+    // Between here and the slot stores, which the rest of the launch waits for, the hot shapes (one
+    // pass of each task loop) wait for LDS and barriers only: the arguments came in with the entry's
+    // batch, each task loop is `if (tid < n) task(tid)` plus a cold loop for the passes after the first
+    // (a loop's preheader got a full vector-memory drain, on this ISA also of the stores just issued),
+    // and every other store (the norm chunks' input, the error flag, Y', z', gp) follows the slot stores,
+    // so that no wait in between has a store to wait for.
     constexpr int ES = kGRec;
     double* sE = rec;
+    // the pair tasks: H = 2^hs lanes share a camera-pair block's row (H | 64)
+    int hs = 0;
+    while (hs < 5 && 6 * nq * (2 << hs) <= (NT < MCC_GROUP_PAIR_THREADS ? NT : MCC_GROUP_PAIR_THREADS)) ++hs;
+    const int H = 1 << hs;
+    // the first pass's task descriptors, read ahead of the barriers in front of their use (phase 0 wrote
+    // seq, sgb, spq and scn and nothing after it does): lanes without a task read entry 0.  (The pair
+    // task's first contribution, whose index comes out of spq, is read behind the next barrier: here its
+    // second round trip would stand in front of the sums' loads.)
+    const bool ut0 = tid < 6 * gne, pt0 = tid < 6 * nq * H;
+    const int ule0 = ut0 ? tid / 6 : 0;
+    const int ueq0 = seq[ule0], ugb0 = sgb[ule0];
+    const int4 pqv0 = spq[pt0 ? (tid >> hs) / 6 : 0];
     // photo q's Hpp / gp column sums in edge order
     if (tid < 27 * np) {
         const int q = tid / 27, col27 = tid % 27;
@@ -1266,10 +1291,16 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
     }
     __syncthreads();
     SSTAMP(stp, 7, 0);
+    const unsigned pw0 = scn[pt0 && (tid & (H - 1)) < pqv0.y ? pqv0.x + (tid & (H - 1)) : 0];
+    double zq[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, gs[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // photo tid's z', gp
+    double ng2 = 0.0, nx2 = 0.0;   // its ||G||^2, ||x||^2 (the fold's: phase 0 left them in sxn)
+    bool npd = false;              // its block is not positive definite (or the test's fault)
     if (tid < np) {   // one lane per photo: Cholesky Hpp = L L^T, Li = L^-1, v = Li gp, z' = Li^T v
         const int q = tid, photo = p0 + q;
-        double A[21], gs[6], Lm[6][6], Li[6][6];
+        double A[21], Lm[6][6], Li[6][6];
         const double2* S2 = reinterpret_cast<const double2*>(s27 + 28 * q);
+        ng2 = sxn[16 * q + 6];
+        nx2 = sxn[16 * q + 7];
 #pragma unroll
         for (int k = 0; k < 14; ++k) {
             const double2 w = S2[k];
@@ -1320,32 +1351,27 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
             double t = 0.0;
 #pragma unroll
             for (int i = j; i < 6; ++i) t += Li[i][j] * vv[i];
-            hp.zp[6 * (size_t)photo + j] = t;
-            hp.gp_tot[6 * (size_t)photo + j] = gs[j];
+            zq[j] = t;
             sv[6 * q + j] = vv[j];
         }
         double2* L2 = reinterpret_cast<double2*>(sLi + 36 * q);
 #pragma unroll
         for (int k = 0; k < 18; ++k) L2[k] = make_double2(Li[(2 * k) / 6][(2 * k) % 6], Li[(2 * k + 1) / 6][(2 * k + 1) % 6]);
-        if (bad || photo == a.fault_photo) atomicOr(&st->error, kErrPhotoNotPD);
-        if (fold) {   // the norm chunk's input: ||G||^2, ||x||^2 and the not-PD flag (sc1, each word its flag)
-            double* fw = a.fnorm + 4 * (size_t)photo;
-            st_sc1_x2(fw, sxn[16 * q + 6], sxn[16 * q + 7]);
-            st_sc1(fw + 2, bad || photo == a.fault_photo ? 1.0 : 0.0);
-        }
+        npd = bad || photo == fault_photo;
     }
     __syncthreads();
     SSTAMP(stp, 8, 0);
-    for (int t = tid; t < 6 * gne; t += NT) {   // task (edge, row i): U row i in place of Hgp row i, Y' row i
+    // task (edge, row i): U row i in place of Hgp row i, Y' row i (eq: the edge's photo, gb: its global block)
+    auto uy_task = [&](const int t, const int eq, const int gb, double (&y)[6]) {
         const int le = t / 6, i = t % 6;
-        double h[6], li[36], u[6], y[6];
+        double h[6], li[36], u[6];
         double2* H2 = reinterpret_cast<double2*>(sE + ES * le + 22 + 6 * i);
-        const double2* I2 = reinterpret_cast<const double2*>(sLi + 36 * seq[le]);
+        const double2* I2 = reinterpret_cast<const double2*>(sLi + 36 * eq);
 #pragma unroll
         for (int q = 0; q < 3; ++q) { const double2 w = H2[q]; h[2 * q] = w.x; h[2 * q + 1] = w.y; }
 #pragma unroll
         for (int q = 0; q < 18; ++q) { const double2 w = I2[q]; li[2 * q] = w.x; li[2 * q + 1] = w.y; }
-        const bool gl = sgb[le] >= 0;
+        const bool gl = gb >= 0;
 #pragma unroll
         for (int j = 0; j < 6; ++j) {   // U[i][j] = sum_{k <= j} Hgp[i][k] Li[j][k]
             double w = 0.0;
@@ -1360,28 +1386,38 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
             for (int k = j; k < 6; ++k) w += u[k] * li[6 * k + j];
             y[j] = w;
         }
-        double2* G2 = reinterpret_cast<double2*>(hp.Y + 36 * (size_t)(ge0 + le) + 6 * i);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            H2[q] = make_double2(u[2 * q], u[2 * q + 1]);
-            G2[q] = make_double2(y[2 * q], y[2 * q + 1]);
-        }
+        for (int q = 0; q < 3; ++q) H2[q] = make_double2(u[2 * q], u[2 * q + 1]);
+    };
+    auto store_y = [&](const int t, const double (&y)[6]) {   // Y' row (t % 6) of edge t / 6: the next launch reads it
+        double2* G2 = reinterpret_cast<double2*>(hp.Y + 6 * (size_t)(6 * ge0 + t));
+#pragma unroll
+        for (int q = 0; q < 3; ++q) G2[q] = make_double2(y[2 * q], y[2 * q + 1]);
+    };
+    double yl[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (ut0) {
+        uy_task(tid, ueq0, ugb0, yl);
+    }
+#pragma unroll 1
+    for (int t = tid + NT; t < 6 * gne; t += NT) {   // cold: more than NT / 6 edges (16 lanes per edge)
+        double y[6];
+        uy_task(t, seq[t / 6], sgb[t / 6], y);
+        store_y(t, y);
     }
     __syncthreads();
     SSTAMP(stp, 9, 0);
-    // the group's Schur pair products per camera-pair block -> its slot (k_photo's pair tasks)
-    int H = 1;
-    while (H < 32 && 6 * nq * 2 * H <= (NT < MCC_GROUP_PAIR_THREADS ? NT : MCC_GROUP_PAIR_THREADS)) H *= 2;
-    for (int t = tid; t < 6 * nq * H; t += NT) {
-        const int h = t % H, k = t / H / 6, i0 = (t / H) % 6;
-        const int4 pqv = spq[k];   // {first contribution, count, diagonal block << 1, slot offset}
+    // the group's Schur pair products per camera-pair block -> its slot (k_photo's pair tasks); pqv is
+    // spq[t / H / 6], w the task's first contribution scn[pqv.x + t % H] (read only if it has one)
+    auto pair_task = [&](const int t, const int4 pqv, unsigned w) {
+        const int h = t & (H - 1), i0 = (t >> hs) % 6;
+        // pqv: {first contribution, count, diagonal block << 1, slot offset}
         const bool diag = (pqv.z & 2) != 0;
         double acc[6], racc = 0.0, jacc = 0.0;
 #pragma unroll
         for (int j = 0; j < 6; ++j) acc[j] = 0.0;
 #pragma unroll 1
         for (int c = pqv.x + h; c < pqv.x + pqv.y; c += H) {
-            const unsigned w = scn[c];
+            const unsigned wn = c + H < pqv.x + pqv.y ? scn[c + H] : 0u;   // (the next one's, ahead of this one's operands)
             const int ea = w & 255, eb = (w >> 8) & 255, q = w >> 17;
             const bool self = (w >> 16) & 1;
             const double2* Y2 = reinterpret_cast<const double2*>(sE + ES * ea + 22 + 6 * i0);
@@ -1413,6 +1449,7 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
                 racc += gg - d;
                 jacc += gg;
             }
+            w = wn;
         }
         for (int o = 1; o < H; o <<= 1) {   // the H parts are lanes t - h .. t - h + H - 1 (H | 64)
 #pragma unroll
@@ -1421,7 +1458,7 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
             jacc += __shfl_xor(jacc, o);
         }
         if (h == 0) {   // write-through (sc1): the folded items poll these words in this launch
-            double* out = a.pairprod + (size_t)pqv.w;
+            double* out = pairprod + (size_t)pqv.w;
 #ifdef MCC_SLOT_PLAIN   // (A/B builds only)
 #pragma unroll
             for (int j = 0; j < 6; ++j) out[i0 * 6 + j] = acc[j];
@@ -1437,6 +1474,32 @@ __device__ __forceinline__ bool group_body(State* st, const int* __restrict__ gh
                 st_sc1(out + 42 + i0, jacc);
             }
 #endif
+        }
+    };
+    if (pt0) pair_task(tid, pqv0, pw0);
+#pragma unroll 1
+    for (int t = tid + NT; t < 6 * nq * H; t += NT) {   // cold: more than NT / 6 camera-pair blocks (H = 1 there)
+        const int4 pqv = spq[(t >> hs) / 6];
+        pair_task(t, pqv, scn[(t & (H - 1)) < pqv.y ? pqv.x + (t & (H - 1)) : 0]);
+    }
+    SSTAMP(stp, 11, 0);   // wave 0's slot stores issued
+    // Every other store of the phase, all operands in registers.  First what this launch still reads, the
+    // norm chunks' input (||G||^2, ||x||^2 and the not-PD flag: sc1, each word its flag; the fold takes
+    // the flag from here, not from state->error), then the error flag and what the next launch reads
+    if (tid < np) {
+        if (fold) {
+            double* fw = fnorm + 4 * (size_t)(p0 + tid);
+            st_sc1_x2(fw, ng2, nx2);
+            st_sc1(fw + 2, npd ? 1.0 : 0.0);
+        }
+        if (npd) atomicOr(&st->error, kErrPhotoNotPD);
+    }
+    if (ut0) store_y(tid, yl);
+    if (tid < np) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            hp.zp[6 * (size_t)(p0 + tid) + j] = zq[j];
+            hp.gp_tot[6 * (size_t)(p0 + tid) + j] = gs[j];
         }
     }
 #ifdef MCC_DIAG

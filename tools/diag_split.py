@@ -6,7 +6,8 @@ diagnostic build (libmcc_diag.so).  Never quote this build's run time: read its 
 
 k_group (the split step's group kernel) group g -> row g slots 0..10 (start, loads, photo update and
 Rodrigues, round 0's prologue, sweep, chain, the later rounds, Hpp sums, Cholesky, U / Y', pairs), all
-stamped by wave 0; slots 12 and 13 the clock at the kernel's first instruction as wave 0 and the last wave
+stamped by wave 0; slot 11 wave 0's slot stores issued (slot 10 stands behind a drain of the stores that
+only this build has); slots 12 and 13 the clock at the kernel's first instruction as wave 0 and the last wave
 read it (printed as "entry -> stamp 0": the role dispatch, the stop test and the scalar loads, which the
 phase rows do not cover); slots 16 + w wave w's last round's end and 24 + w its round-0 prologue, sweep and chain
 ends, printed per wave half (wave_halves).
@@ -101,6 +102,11 @@ def main():
         phases(list(range(11)), ["loads (round trip 1)", "photo update+Rodrigues", "edge prologue (r0)", "sweep (r0)",
                                  "butterfly+chain (r0)", "later rounds", "photo Hpp sums", "Cholesky", "U, Y'",
                                  "pairs+store"], f"k_group ({ng} groups)")
+        # slot 11: wave 0's slot stores issued (stamp 10 stands behind the diagnostic build's own drain)
+        ok = (s[:, 9] > 0) & (s[:, 11] > 0)
+        if ok.any():
+            print(f"  {'pairs, to the issue':22s} {med(s[ok, 11] - s[ok, 9])}")
+            print(f"  {'stamp 0 -> the issue':22s} {med(s[ok, 11] - s[ok, 0])}")
         wave_halves(raw[:32 * nv].reshape(nv, 32), ng)
         return
     phases([0, 1, 3, 4, 5], ["load+stage+sums", "Cholesky, Li", "U, Y'", "pairs+store"], "k_photo")

@@ -16,7 +16,11 @@ leave equal.  The kernel's VGPR count and SGPR spill count come from the listing
 
     python3 tools/edge_round_counts.py part3.s [mangled-name substring] --entry [listing.txt]
 
-counts the scalar loads and waits of the kernel's entry and of phase 0's vector batch instead (entry())."""
+counts the scalar loads and waits of the kernel's entry and of phase 0's vector batch instead (entry()).
+
+    python3 tools/edge_round_counts.py part3.s [mangled-name substring] --photo
+
+counts the photo phase that follows the rounds, up to the group's last slot store (photo())."""
 import collections
 import re
 import sys
@@ -94,10 +98,98 @@ def entry(k, lines, pat, out):
                     f.write(f"{i + 1}:{l.split(';')[0].rstrip() if not l.strip().startswith(';') else l}\n")
 
 
+def photo(k, lines, pat):
+    """--photo: the photo phase, from the barrier that ends the rounds (the fourth s_barrier) to the group
+    path's last slot store: the last write-through (sc1) global store between the barrier behind U, Y'
+    (the seventh) and the next one.  In the listing's own order, as the other modes: a block the
+    compiler laid out inside the region counts whether or not the 32-lane shapes take it, so every wait
+    and scalar load is printed with its line and the label it stands under, for the reader to place."""
+    ops = [op_of(l) for l in k]
+    bars = [i for i, o in enumerate(ops) if o == "s_barrier"]
+    assert len(bars) > 7, "k_group has at least eight barriers"
+    b0, b3 = bars[3], bars[6]
+    # task loops: the outermost loops (backward branches) with a global store in their body.  Where the
+    # task loops start at the thread's own index they are the first pass and the tasks' only copy;
+    # where the first pass stands outside as `if (tid < n) task(tid)`, they are the cold passes after it
+    labels = {l.split(":")[0]: i for i, l in enumerate(k) if re.match(r"^\.LBB\d+_\d+:", l)}
+    loops = []
+    for i in range(b0, bars[7]):
+        m = re.match(r"\s+s_cbranch_\S+\s+(\.LBB\d+_\d+)", k[i])
+        if m and m.group(1) in labels and b0 <= labels[m.group(1)] < i:
+            loops.append((labels[m.group(1)], i))
+    loops = [(h, e) for h, e in loops if any(ops[j] and ops[j].startswith("global_store") for j in range(h, e))]
+    loops = [(h, e) for h, e in loops if not any((h2, e2) != (h, e) and h2 <= h and e <= e2 for h2, e2 in loops)]
+    in_loop = lambda i: any(h <= i <= e for h, e in loops)   # noqa: E731
+    slots = [i for i in range(b3, bars[7]) if ops[i] and ops[i].startswith("global_store") and " sc1" in k[i].split(";")[0]]
+    assert slots, "no write-through store behind the barrier that follows U, Y'"
+    # the first pass stands outside the task loops where a 16-byte slot store does; the region then ends
+    # at the last write-through store ahead of the pair tasks' cold loop (the last task loop)
+    cold = any("dwordx4" in k[i] and not in_loop(i) for i in slots)
+    if cold:
+        slots = [i for i in slots if not in_loop(i) and i < loops[-1][0]]
+    end = slots[-1] + 1
+    if cold:
+        ops = [None if in_loop(i) else o for i, o in enumerate(ops)]
+    print("task loops (a global store inside) at lines " + ", ".join(f"{h + 1}..{e + 1}" for h, e in loops) +
+          (": the passes after the first, NOT counted below" if cold else ": the tasks' only copy, counted below"))
+    names = ("Hpp sums", "Cholesky", "U, Y'", "pairs + store")
+    cuts = [b0, bars[4], bars[5], b3, end]
+    print(f"kernel {pat}: photo phase, lines {b0 + 1}..{end} (barriers at {[b + 1 for b in bars[3:7]]}, last slot store at {end})")
+
+    def under(i):
+        return next((k[j].split(":")[0] for j in range(i, -1, -1) if re.match(r"^\.LBB\d+_\d+:", k[j])), "-")
+
+    def kind(l):
+        t = l.split(";")[0]
+        out = []
+        m = re.search(r"vmcnt\((\d+)\)", t)
+        if m:
+            out.append("vmcnt(0)" if m.group(1) == "0" else "vmcnt(n)")
+        m = re.search(r"lgkmcnt\((\d+)\)", t)
+        if m:
+            out.append("lgkmcnt(0)" if m.group(1) == "0" else "lgkmcnt(n)")
+        return out
+
+    print(f"{'row':14s} {'VALU':>5s} {'FP64':>5s} {'s_load':>7s} {'vmcnt(0)':>9s} {'vmcnt(n)':>9s} {'lgkmcnt(0)':>11s} {'lgkmcnt(n)':>11s} "
+          f"{'ds_bpermute':>12s} {'ds other':>9s} {'v_readlane':>11s} {'dpp/permlane':>13s}")
+    for name, a, b in list(zip(names, cuts, cuts[1:])) + [("all", b0, end)]:
+        r = [(i, o) for i, o in enumerate(ops[a:b], a) if o]
+        c = classify([o for _, o in r])
+        w = collections.Counter(x for i, o in r if o == "s_waitcnt" for x in kind(k[i]))
+        print(f"{name:14s} {c['valu']:5d} {c['fp64']:5d} {sum(o.startswith('s_load') for _, o in r):7d} {w['vmcnt(0)']:9d} "
+              f"{w['vmcnt(n)']:9d} {w['lgkmcnt(0)']:11d} {w['lgkmcnt(n)']:11d} {sum(o.startswith('ds_bpermute') for _, o in r):12d} "
+              f"{sum(o.startswith('ds_') and not o.startswith('ds_bpermute') for _, o in r):9d} "
+              f"{sum(o == 'v_readlane_b32' for _, o in r):11d} {sum('_dpp' in o or 'permlane' in o for _, o in r):13d}")
+    r = [(i, o) for i, o in enumerate(ops[b0:end], b0) if o]
+    print("scalar loads and vector-memory waits (line, label above, text):")
+    for i, o in r:
+        if o.startswith("s_load") or (o == "s_waitcnt" and "vmcnt" in k[i].split(";")[0]):
+            print(f"  {i + 1:6d} {under(i):12s} {k[i].split(';')[0].strip()}")
+    print("global stores and atomics in order (line, label above, text):")
+    for i, o in r:
+        if o.startswith(("global_store", "global_atomic", "flat_store", "flat_atomic")):
+            print(f"  {i + 1:6d} {under(i):12s} {' '.join(k[i].split(';')[0].split())}")
+    h = collections.Counter(o for _, o in r if o.startswith("v_") and "_f64" in o)
+    print("FP64: " + "  ".join(f"{o} {n}" for o, n in sorted(h.items())))
+    meta = "\n".join(lines)
+    for key in ("num_vgpr", "numbered_sgpr", "private_seg_size"):
+        m = re.search(re.escape(pat) + r"\S*\." + key + r", (\d+)", meta)
+        if m:
+            print(key, m.group(1))
+    m = re.search(re.escape(pat) + r".*?sgpr_spill_count:?\s+(\d+)", meta, re.S)
+    if m:
+        print("sgpr_spill_count", m.group(1))
+    print(f"whole kernel: v_writelane_b32 {sum('v_writelane_b32' in l for l in k)}  v_readlane_b32 {sum('v_readlane_b32' in l for l in k)}")
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     hist = "--hist" in sys.argv
     lines = open(args[0]).read().splitlines()
+    if "--photo" in sys.argv:
+        pat = args[1] if len(args) > 1 else DEFAULT
+        photo(kernel_text(lines, pat), lines, pat)
+        return
     if "--entry" in sys.argv:
         pat = args[1] if len(args) > 1 and not args[1].endswith(".txt") else DEFAULT
         out = next((a for a in args[1:] if a.endswith(".txt")), None)
